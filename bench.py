@@ -15,12 +15,17 @@ before anything touches a GPU).  `--config cfg5` is BASELINE config 5's per-GPU 
 4096^2 per GPU and step (1024 images over 8 GPUs).  `--scaling strong` fixes the TOTAL batch (--batch
 images split over the ranks) instead of the per-GPU batch.
 
-Rank 0 prints ONE JSON line: the contract's keys plus
+A plain run does what the headline figure needs and nothing else: it sets up, pre-heats and warms up, times ONE
+region of exactly K steps and prints ONE JSON line (rank 0) with the contract's keys.  `--full` adds, in the same line:
+  config.timed_regions_ms  three timed regions of K steps each; the line's figure is then their median
   roofline      dominant kernel: algorithmic bytes per launch / HIP-event duration vs 8 TB/s
   cpu_baseline  the C oracle (a port of the reference's algorithm) timed on this host's cores
   end_to_end    algorithmic bytes of the whole step / step time, cold (no pre-heat) step time
   extra         (1 GPU) one-thread CPU baseline, quoted / measured pywt, PCIe transfers and the reference's
-                own benchmark method (set_image + forward + coeffs), a working set beyond the Infinity Cache
+                own benchmark method (set_image + forward + coeffs), the other configurations, a working set beyond
+                the Infinity Cache
+`--dump-outputs DIR` writes what the last timed step computed (the reconstructed images, see dump_outputs) as .npy files.
+The seeded input is generated again before every timed region, so the same arguments give the same outputs run to run.
 """
 import argparse
 import json
@@ -215,9 +220,15 @@ def parse_args(argv=None):
                          "interval to compare ranks on")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch images per GPU; strong: --batch images in total, split over the ranks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline figure: cold step time, three timed regions, per-kernel profile and "
+                         "roofline, CPU baselines, `extra` (other configurations, PCIe, larger batches), the one-GPU scaling "
+                         "reference of a multi-rank run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the images the last timed step reconstructed to DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the `extra` measurements (one-thread CPU, pywt, PCIe, beyond-Infinity-Cache batch)")
+                    help="(--full) skip the `extra` measurements (one-thread CPU, pywt, PCIe, beyond-Infinity-Cache batch)")
     ap.add_argument("--preheat-ms", type=float, default=200.0,
                     help="run the workload untimed for this long before the warmup steps: after an idle period "
                          "the GPU needs tens of ms to ramp its clocks, and W = 10 steps last under 1 ms")
@@ -487,7 +498,7 @@ def timed_steps(step, device_sync, steps):
     return (time.perf_counter() - t0) / steps
 
 
-def timed_region(step, device_sync, steps, dist, backend, before_closing_barrier=None, reheat=None):
+def timed_region(step, device_sync, steps, dist, backend, before_closing_barrier=None, reheat=None, reset=None):
     """The contract's timed region, the SAME code for one rank and for N: barrier + device sync, t0, exactly
     `steps` steps, device sync, t1, then the closing barrier + device sync.  Every rank's clock stops at t1,
     BEFORE the closing barrier: that barrier (an RCCL all-reduce kernel + a host sync, 50-100 us) only lines the
@@ -498,11 +509,16 @@ def timed_region(step, device_sync, steps, dist, backend, before_closing_barrier
     barrier also builds the RCCL communicator: hundreds of ms), and an MI355X that has idled for ~20 ms runs the next
     milliseconds 10 % slower (profiles/r03c_distgap.txt: 70.1 -> 77.4 us per step after a 20 ms sleep).  So the ranks
     are lined up TWICE: barrier, the same untimed re-heat on every rank (they stay together), then the barrier that
-    opens the interval, which nobody waits in for more than its own latency."""
+    opens the interval, which nobody waits in for more than its own latency.
+
+    `reset`: untimed, right before the opening barrier -- the step transforms its own output again, so the input of the
+    timed steps is regenerated here to make what they compute independent of how many steps ran before."""
     if dist is not None and reheat is not None:
         barrier(dist, backend)
         device_sync()
         reheat()
+    if reset is not None:
+        reset()
     barrier(dist, backend)
     device_sync()
     t0 = time.perf_counter()
@@ -515,6 +531,30 @@ def timed_region(step, device_sync, steps, dist, backend, before_closing_barrier
     barrier(dist, backend)
     device_sync()
     return max_over_ranks(elapsed, dist, backend)
+
+
+DUMP_MAX_VALUES = 1 << 22  # per dumped image: 16 MiB of float32, so the two images of a dump stay far inside 64 MB
+DUMP_SEED = 20240 + 5
+
+
+def dump_outputs(outdir, image_at, batch, Nr, Nc):
+    """--dump-outputs: what a caller of the timed step receives from its last call -- the image `inverse` reconstructed --
+    for the first and the last image of the batch, as DIR/image<b>.npy (float32, shape (Nr, Nc)).  An image of more than
+    DUMP_MAX_VALUES samples (4096^2 is 64 MiB) is cut to DIR/image<b>_sample.npy: the values at DUMP_MAX_VALUES positions
+    drawn with the fixed seed DUMP_SEED, in ascending order of position, the same positions in every run.  Returns the paths."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    n = Nr * Nc
+    pick = None
+    if n > DUMP_MAX_VALUES:
+        pick = np.sort(np.random.RandomState(DUMP_SEED).choice(n, DUMP_MAX_VALUES, replace=False))
+    paths = []
+    for b in sorted({0, batch - 1}):
+        img = np.asarray(image_at(b), dtype=np.float32).reshape(Nr, Nc)
+        path = os.path.join(outdir, "image%d.npy" % b if pick is None else "image%d_sample.npy" % b)
+        np.save(path, img if pick is None else img.ravel()[pick])
+        paths.append(path)
+    return paths
 
 
 def beyond_mall(cfg, device, steps, B=16):
@@ -767,13 +807,14 @@ def dry_run(args, rank, world, dist, backend, out_stream=None):
     B, first, total = rank_batch(args, world, rank)
     step = lambda: time.sleep(0.001 * (1 + rank))
     alone_s = None
-    if dist is not None:  # the same-workload one-rank reference, as in the real run
+    if dist is not None and args.full:  # the same-workload one-rank reference, as in the real run
         barrier(dist, backend)
         if rank == 0:
             alone_s = median([timed_steps(step, lambda: None, args.steps) for _ in range(3)])
         barrier(dist, backend)
     regions = [timed_region(step, lambda: None, args.steps, dist, backend,
-                            before_closing_barrier=lambda: time.sleep(1e-3 * rank * args.dry_run_barrier_skew_ms)) for _ in range(3)]
+                            before_closing_barrier=lambda: time.sleep(1e-3 * rank * args.dry_run_barrier_skew_ms))
+               for _ in range(3 if args.full else 1)]
     dt = median(regions)
     if rank == 0:
         samples = total * cfg[0] * cfg[1]
@@ -814,7 +855,10 @@ def single_process_main(args, out_stream):
     total = b if args.scaling == "strong" else b * n
     shared_gpu = os.environ.get("PDWT_BENCH_SHARE_GPU") == "1"
     S = ShardedBatch(total, Nr, Nc, wname, L, devices=[0] * n if shared_gpu else list(range(n)), do_swt=swt, ndim=ndim)
-    S.fill_hash(20240 + 2, 255.0)
+
+    def fill_input():
+        S.fill_hash(20240 + 2, 255.0)
+    fill_input()
 
     def step():
         S.forward()
@@ -822,9 +866,11 @@ def single_process_main(args, out_stream):
             S.soft_threshold(beta)
         S.inverse()
 
-    for _ in range(args.warmup):
-        step()
-    cold_s = timed_steps(step, S.synchronize, args.steps)
+    cold_s = None
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        cold_s = timed_steps(step, S.synchronize, args.steps)
     t_pre = time.perf_counter()
     while (time.perf_counter() - t_pre) * 1e3 < args.preheat_ms:
         for _ in range(20):
@@ -832,20 +878,11 @@ def single_process_main(args, out_stream):
         S.synchronize()
     for _ in range(args.warmup):
         step()
+    fill_input()
     step_s = timed_steps(step, S.synchronize, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, S.image_at, total, Nr, Nc)
     samples = total * Nr * Nc
-    p0 = S.plans[0]
-
-    def step0():
-        p0.forward()
-        if beta is not None:
-            p0.soft_threshold(beta)
-        p0.inverse()
-
-    kernels, roofline, step_names = kernel_profile(p0, step0, cfg, args.config, p0.batch, args.steps)
-    thr_separate = any(nm.startswith("soft_threshold") for nm in step_names)
-    bps = algorithmic_bytes_per_sample(cfg, threshold_separate=thr_separate)
-    per_gpu_bytes = bps * max(hi - lo for _, lo, hi in S.shards) * Nr * Nc
     out = {
         "metric": metric_name(args.config, desc, b),
         "value": samples / step_s / 1e6, "unit": "Msamples/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
@@ -856,16 +893,29 @@ def single_process_main(args, out_stream):
                    "parallelism": "image-sharded x%d, ONE process (pypwt_amd.ShardedBatch: one plan + stream + host thread "
                                   "per GPU), no collectives" % n,
                    "preheat_ms": args.preheat_ms, "timed_region_ms": step_s * args.steps * 1e3},
-        "roofline": roofline,
-        "end_to_end": {"algorithmic_bytes_per_sample": bps, "GBps_per_gpu": per_gpu_bytes / step_s / 1e9,
-                       "frac_of_hbm_peak": per_gpu_bytes / step_s / 1e9 / HBM_PEAK_GBPS,
-                       "cold_ms_per_step": cold_s * 1e3},
-        "kernels": kernels[:12],
     }
     if shared_gpu:
         out["config"]["shared_gpu_test_run"] = "all shards ran on GPU 0 (PDWT_BENCH_SHARE_GPU=1): not a multi-GPU measurement"
-    if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(cfg)
+    if args.full:
+        p0 = S.plans[0]
+
+        def step0():
+            p0.forward()
+            if beta is not None:
+                p0.soft_threshold(beta)
+            p0.inverse()
+
+        kernels, roofline, step_names = kernel_profile(p0, step0, cfg, args.config, p0.batch, args.steps)
+        thr_separate = any(nm.startswith("soft_threshold") for nm in step_names)
+        bps = algorithmic_bytes_per_sample(cfg, threshold_separate=thr_separate)
+        per_gpu_bytes = bps * max(hi - lo for _, lo, hi in S.shards) * Nr * Nc
+        out["roofline"] = roofline
+        out["end_to_end"] = {"algorithmic_bytes_per_sample": bps, "GBps_per_gpu": per_gpu_bytes / step_s / 1e9,
+                             "frac_of_hbm_peak": per_gpu_bytes / step_s / 1e9 / HBM_PEAK_GBPS,
+                             "cold_ms_per_step": cold_s * 1e3}
+        out["kernels"] = kernels[:12]
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(cfg)
     print(json.dumps(out), file=out_stream, flush=True)
     S.cleanup()
     return 0
@@ -884,6 +934,8 @@ def main():
               % (args.gpus, world, world, world), file=sys.stderr)
     resolve_config(args, world)
     if args.dry_run:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs needs the GPU path (a dry run computes nothing)")
         dry_run(args, rank, world, dist, backend, out_stream)
         if dist is not None:
             dist.destroy_process_group()
@@ -901,8 +953,10 @@ def main():
     # barriers and the aggregation on real hardware; the figure it prints is NOT a multi-GPU measurement and says so
     shared_gpu = world > 1 and os.environ.get("PDWT_BENCH_SHARE_GPU") == "1"
     plan = BatchedWavelets(B, Nr, Nc, wname, L, do_swt=swt, ndim=ndim, device=0 if shared_gpu else local_rank)
-    # deterministic synthetic input generated ON the device; every rank gets different images
-    plan.fill_hash(20240 + 2, 255.0, index_offset=first_image * Nr * Nc)
+
+    def fill_input():  # deterministic synthetic input generated ON the device; every rank gets different images
+        plan.fill_hash(20240 + 2, 255.0, index_offset=first_image * Nr * Nc)
+    fill_input()
 
     def step():
         plan.forward()
@@ -917,10 +971,11 @@ def main():
             torch.cuda.synchronize()
 
     barrier(dist, backend)  # builds the RCCL communicator now, not inside the measurement
-    # cold figure: W warm-up steps after an idle period, then K steps (no pre-heat): what a one-shot caller sees
-    for _ in range(args.warmup):
-        step()
-    cold_s = timed_steps(step, device_sync, args.steps)
+    cold_s = None
+    if args.full:  # cold figure: W warm-up steps after an idle period, then K steps (no pre-heat): what a one-shot caller sees
+        for _ in range(args.warmup):
+            step()
+        cold_s = timed_steps(step, device_sync, args.steps)
 
     # pre-heat (untimed): sustained-throughput conditions for the timed steps
     t_pre = time.perf_counter()
@@ -943,7 +998,7 @@ def main():
     # their GPUs idle), so that the line carries the denominator of its own scaling efficiency -- value(N) / value(1) of two
     # different default workloads (one image on one GPU, 128 per GPU on several) says nothing.
     alone_s = None
-    if dist is not None:
+    if dist is not None and args.full:
         barrier(dist, backend)
         if rank == 0:
             reheat()
@@ -951,39 +1006,17 @@ def main():
         barrier(dist, backend)
         reheat()
 
-    # THREE timed regions, always, each the contract's (barrier, K steps, barrier): the line's figure is their median and all
-    # three are in the line (a one-sided "time again when slow" would bias the figure downwards).
-    timed_regions = [timed_region(step, device_sync, args.steps, dist, backend, reheat=reheat) for _ in range(3)]
+    # One timed region, the contract's (barrier, K steps, barrier); with --full THREE, always: the line's figure is their
+    # median and all three are in the line (a one-sided "time again when slow" would bias the figure downwards).
+    timed_regions = [timed_region(step, device_sync, args.steps, dist, backend, reheat=reheat, reset=fill_input)
+                     for _ in range(3 if args.full else 1)]
     dt = median(timed_regions)
-    cold_s = max_over_ranks(cold_s, dist, backend)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan.image_at, B, Nr, Nc)
 
     step_s = dt / args.steps
     samples_per_step = total_images * Nr * Nc
     value = samples_per_step / step_s / 1e6
-
-    kernels, roofline, step_names = kernel_profile(plan, step, cfg, args.config, B, args.steps, step_us=step_s * 1e6)
-    # the soft threshold costs bytes only when it ran as its own sweep (a `soft_threshold` launch in the step)
-    thr_separate = any(n.startswith("soft_threshold") for n in step_names)
-    bps = algorithmic_bytes_per_sample(cfg, threshold_separate=thr_separate)
-    e2e_bytes = bps * B * Nr * Nc  # per GPU per step
-    e2e = {"algorithmic_bytes_per_sample": bps, "algorithmic_bytes_per_step_per_gpu": e2e_bytes,
-           "GBps_per_gpu": e2e_bytes / step_s / 1e9,
-           "frac_of_hbm_peak": e2e_bytes / step_s / 1e9 / HBM_PEAK_GBPS,
-           "cold_ms_per_step": cold_s * 1e3, "cold_Msamples_s": samples_per_step / cold_s / 1e6,
-           "per_level_streaming_bytes_per_sample": per_level_streaming_bytes_per_sample(cfg, thr_separate),
-           "sum_kernel_us": sum(k["avg_us"] for k in kernels)}
-    if roofline.get("copy_ceiling_GBps"):
-        e2e["frac_of_copy_ceiling"] = e2e["GBps_per_gpu"] / roofline["copy_ceiling_GBps"]
-    if roofline.get("step_copy_floor_us"):
-        # every launch of the step replaced by a flat copy of its algorithmic bytes, timed in this run on these buffers:
-        # the step cannot be expected below this with one launch per level (group)
-        e2e["copy_floor_us_per_step"] = roofline["step_copy_floor_us"]
-        e2e["copy_floor_over_step"] = roofline["step_copy_floor_us"] * 1e-6 / step_s
-    if swt and beta is not None:
-        e2e["threshold"] = ("separate sweep" if thr_separate else
-                            "folded into the inverse's loads (no launch, no bytes); as a separate sweep the step "
-                            "would be charged %.0f B/sample" % algorithmic_bytes_per_sample(cfg, True))
-
     workload = args.config if args.config != "cfg5" else "cfg5 (per-GPU shard of cfg2 images)"
     out = {
         "metric": metric_name(args.config, desc, B),
@@ -994,18 +1027,43 @@ def main():
                    "wavelet": wname, "levels": L, "shape": [Nr, Nc],
                    "parallelism": "image-sharded x%d, no collectives" % world, "preheat_ms": args.preheat_ms,
                    "timed_region_ms": dt * 1e3, "timed_regions_ms": [t * 1e3 for t in timed_regions],
-                   "timed_region_rule": "median of three regions of `steps` steps each"},
-
-        "roofline": roofline, "end_to_end": e2e, "kernels": kernels[:12],
+                   "timed_region_rule": ("median of three regions of `steps` steps each" if args.full else
+                                         "one region of `steps` steps")},
     }
-    if args.config in ("cfg2", "cfg5"):  # the configurations the north star is stated on
-        out["target"] = target_record(e2e["frac_of_hbm_peak"], e2e_bytes, roofline.get("step_copy_floor_us"))
-    if alone_s is not None:
-        one = B * Nr * Nc / alone_s / 1e6
-        out["scaling_reference"] = {"one_gpu_same_workload_Msamples_s": one, "one_gpu_same_workload_ms_per_step": alone_s * 1e3,
-                                    "efficiency": value / (world * one),
-                                    "note": "rank 0 alone on its shard of %d images per step (the other ranks waiting at a barrier), median "
-                                            "of three regions; efficiency = value / (n_gpus x that)" % B}
+    if args.full:
+        cold_s = max_over_ranks(cold_s, dist, backend)
+        kernels, roofline, step_names = kernel_profile(plan, step, cfg, args.config, B, args.steps, step_us=step_s * 1e6)
+        # the soft threshold costs bytes only when it ran as its own sweep (a `soft_threshold` launch in the step)
+        thr_separate = any(n.startswith("soft_threshold") for n in step_names)
+        bps = algorithmic_bytes_per_sample(cfg, threshold_separate=thr_separate)
+        e2e_bytes = bps * B * Nr * Nc  # per GPU per step
+        e2e = {"algorithmic_bytes_per_sample": bps, "algorithmic_bytes_per_step_per_gpu": e2e_bytes,
+               "GBps_per_gpu": e2e_bytes / step_s / 1e9,
+               "frac_of_hbm_peak": e2e_bytes / step_s / 1e9 / HBM_PEAK_GBPS,
+               "cold_ms_per_step": cold_s * 1e3, "cold_Msamples_s": samples_per_step / cold_s / 1e6,
+               "per_level_streaming_bytes_per_sample": per_level_streaming_bytes_per_sample(cfg, thr_separate),
+               "sum_kernel_us": sum(k["avg_us"] for k in kernels)}
+        if roofline.get("copy_ceiling_GBps"):
+            e2e["frac_of_copy_ceiling"] = e2e["GBps_per_gpu"] / roofline["copy_ceiling_GBps"]
+        if roofline.get("step_copy_floor_us"):
+            # every launch of the step replaced by a flat copy of its algorithmic bytes, timed in this run on these buffers:
+            # the step cannot be expected below this with one launch per level (group)
+            e2e["copy_floor_us_per_step"] = roofline["step_copy_floor_us"]
+            e2e["copy_floor_over_step"] = roofline["step_copy_floor_us"] * 1e-6 / step_s
+        if swt and beta is not None:
+            e2e["threshold"] = ("separate sweep" if thr_separate else
+                                "folded into the inverse's loads (no launch, no bytes); as a separate sweep the step "
+                                "would be charged %.0f B/sample" % algorithmic_bytes_per_sample(cfg, True))
+
+        out.update({"roofline": roofline, "end_to_end": e2e, "kernels": kernels[:12]})
+        if args.config in ("cfg2", "cfg5"):  # the configurations the north star is stated on
+            out["target"] = target_record(e2e["frac_of_hbm_peak"], e2e_bytes, roofline.get("step_copy_floor_us"))
+        if alone_s is not None:
+            one = B * Nr * Nc / alone_s / 1e6
+            out["scaling_reference"] = {"one_gpu_same_workload_Msamples_s": one, "one_gpu_same_workload_ms_per_step": alone_s * 1e3,
+                                        "efficiency": value / (world * one),
+                                        "note": "rank 0 alone on its shard of %d images per step (the other ranks waiting at a barrier), median "
+                                                "of three regions; efficiency = value / (n_gpus x that)" % B}
     if dist is not None:
         if shared_gpu:
             out["config"]["shared_gpu_test_run"] = "all ranks ran on GPU 0 (PDWT_BENCH_SHARE_GPU=1): not a multi-GPU measurement"
@@ -1016,9 +1074,9 @@ def main():
                 "the timed region is %.2f ms: rank-to-rank start skew after the barrier (tens of us) is a visible "
                 "share of it; use --steps >= %d or --config cfg5 (128 images per GPU and step) for a scaling figure"
                 % (dt * 1e3, int(20.0 / (step_s * 1e3)) + 1))
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extra = {}
         if not args.no_cpu_baseline:
             extra["cpu_baseline_1thread"] = cpu_baseline(cfg, threads=1)

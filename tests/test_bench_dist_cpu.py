@@ -63,7 +63,7 @@ def _run(cmd):
 def test_dry_run_world2_gloo():
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", "29533", "bench.py", "--gpus", "2",
-                "--steps", "4", "--warmup", "1", "--dry-run"])
+                "--steps", "4", "--warmup", "1", "--dry-run", "--full"])
     assert out["n_gpus"] == 2 and out["steps"] == 4 and out["scaling"] == "weak"
     # rank 1 sleeps 2 ms per step, rank 0 1 ms: the reported time is the MAX over ranks
     assert out["ms_per_step"] >= 1.9
@@ -79,9 +79,42 @@ def test_dry_run_world2_gloo():
 
 
 def test_dry_run_single():
-    out = _run([sys.executable, "bench.py", "--steps", "3", "--dry-run"])
+    out = _run([sys.executable, "bench.py", "--steps", "3", "--dry-run", "--full"])
     assert out["n_gpus"] == 1 and out["vs_baseline"] is None
     assert out["scaling_reference"] is None and len(out["config"]["timed_regions_ms"]) == 3
+    # a plain run times ONE region of exactly --steps steps: ms_per_step is that region over the steps
+    out = _run([sys.executable, "bench.py", "--steps", "3", "--dry-run"])
+    assert out["steps"] == 3 and len(out["config"]["timed_regions_ms"]) == 1
+    assert abs(out["config"]["timed_region_ms"] - 3 * out["ms_per_step"]) < 1e-9 and out["scaling_reference"] is None
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_large_images(tmp_path):
+    """--dump-outputs: float32 .npy files of the first and last image; an image beyond the size limit is cut to the same seeded
+    positions in every run, and the whole dump stays within 64 MB."""
+    import numpy as np
+
+    import bench
+    seen = []
+
+    def image_at(b):
+        seen.append(b)
+        return np.arange(4096 * 4096, dtype=np.float32).reshape(4096, 4096) + b
+    paths = bench.dump_outputs(str(tmp_path / "a"), image_at, 128, 4096, 4096)
+    assert seen == [0, 127] and [os.path.basename(p) for p in paths] == ["image0_sample.npy", "image127_sample.npy"]
+    first = np.load(paths[0])
+    assert first.dtype == np.float32 and first.shape == (bench.DUMP_MAX_VALUES,)
+    assert np.all(np.diff(first) > 0)  # the positions, in ascending order, no repeats
+    assert np.array_equal(np.load(paths[1]), first + 127)
+    again = bench.dump_outputs(str(tmp_path / "b"), image_at, 128, 4096, 4096)
+    assert all(np.array_equal(np.load(p), np.load(q)) for p, q in zip(paths, again))
+    assert sum(os.path.getsize(p) for p in paths) <= 64e6
+    small = bench.dump_outputs(str(tmp_path / "c"), lambda b: np.full((1, 512 * 512), 7.0), 1, 1, 512 * 512)
+    assert [os.path.basename(p) for p in small] == ["image0.npy"]
+    whole = np.load(small[0])
+    assert whole.dtype == np.float32 and whole.shape == (1, 512 * 512) and np.all(whole == 7.0)
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--dry-run", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, cwd=ROOT, timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not os.path.exists(tmp_path / "d")
 
 
 def test_metric_names_the_workload():

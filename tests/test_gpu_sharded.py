@@ -78,7 +78,7 @@ def test_bench_line_names_the_longest_kernel_and_carries_the_measured_ceiling():
     """VERDICT round 3, task 6: `roofline.kernel` is chosen from launches re-timed ALONE (not from event-inflated in-step
     times), the line carries a flat copy of the same footprint timed in the same run, and the step's copy floor."""
     for attempt in range(2):
-        out = _bench("--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-extras", "--preheat-ms", "100")
+        out = _bench("--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extras", "--preheat-ms", "100")
         rf, e2e = out["roofline"], out["end_to_end"]
         # the copy floor is timed once per line: on a box whose other GPU slots are busy a reading can come out above the step it
         # bounds (seen once in ten evidence runs: 82.9 us against 53-54) -- one re-measurement, then the assertions below decide
@@ -111,12 +111,12 @@ def test_bench_single_process_sharded_over_the_one_gpu():
 
 
 def test_bench_default_line_carries_every_baseline_configuration():
-    """VERDICT round 4, task 2: the driver's own invocation (no flags but steps / warmup) puts all five BASELINE
+    """VERDICT round 4, task 2: the full run (--full, no other flags but steps / warmup) puts all five BASELINE
     configurations on ONE line -- cfg2 as the headline, cfg1 / cfg3 / cfg4 under extra.configs with their step time, roofline
     fraction, dominant kernel and copy floor, cfg5's shard under extra.cfg5_shard_one_gpu -- within seconds."""
     import time
     t0 = time.time()
-    out = _bench("--steps", "20", "--warmup", "5", "--no-cpu-baseline")
+    out = _bench("--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline")
     wall = time.time() - t0
     assert "cfg2" in out["metric"] and len(out["config"]["timed_regions_ms"]) == 3
     cfgs = out["extra"]["configs"]
@@ -128,3 +128,31 @@ def test_bench_default_line_carries_every_baseline_configuration():
         assert len(c["timed_regions_ms_per_step"]) == 3
     assert "cfg5_shard_one_gpu" in out["extra"]
     assert wall < 60, wall  # python start-up + plan creation included; the measurements themselves are a few seconds
+
+
+def test_bench_plain_line_times_exactly_the_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run: the contract's keys, ONE timed region of exactly --steps steps, none of --full's measurements.
+    --dump-outputs: the image the last timed step reconstructed, the same whatever number of untimed steps ran before
+    (another pre-heat), and what the CPU oracle computes for those steps (cfg4: SWT forward, soft threshold, inverse)."""
+    dumps = []
+    for preheat in ("0", "50"):
+        d = str(tmp_path / ("preheat" + preheat))
+        out = _bench("--config", "cfg4", "--steps", "2", "--warmup", "1", "--preheat-ms", preheat, "--dump-outputs", d)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["steps"] == 2 and out["value"] > 0 and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert len(out["config"]["timed_regions_ms"]) == 1
+        assert abs(out["config"]["timed_region_ms"] - 2 * out["ms_per_step"]) < 1e-9
+        assert not {"roofline", "end_to_end", "kernels", "target", "cpu_baseline", "extra"} & set(out), sorted(out)
+        assert sorted(os.listdir(d)) == ["image0.npy"]
+        dumps.append(np.load(os.path.join(d, "image0.npy")))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2048, 2048)
+    assert np.array_equal(dumps[0], dumps[1])
+    import bench
+    Nr, Nc, wname, L, swt, ndim, beta, _ = bench.CONFIGS["cfg4"]
+    oracle.build()
+    x = oracle.hash_input((Nr, Nc), 20240 + 2, scale=255.0)
+    for _ in range(2):
+        bands = oracle.threshold(oracle.forward(x, wname, L, do_swt=swt), (Nr, Nc), L, "soft", beta, do_swt=swt)
+        x = oracle.inverse(bands, (Nr, Nc), wname, L, do_swt=swt)
+    assert np.abs(dumps[0] - x).max() <= 2e-5 * 255 * 3 * 2

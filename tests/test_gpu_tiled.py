@@ -168,7 +168,7 @@ def test_bench_two_ranks_on_the_gpu_box(config, extra):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--config", config,
-                        "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras", "--preheat-ms", "20"] + extra,
+                        "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras", "--preheat-ms", "20"] + extra,
                        capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

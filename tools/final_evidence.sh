@@ -13,13 +13,13 @@ export TMPDIR=/tmp
 timeout 1500 python3 -m pytest tests -q -m gpu > "$OUT/pytest.log" 2>&1 || echo "pytest exit $?" >> "$OUT/pytest.log"
 grep -E "passed|failed|error" "$OUT/pytest.log" | tail -2
 timeout 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || echo "smoke exit $?"
-timeout 400 python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || echo "bench default exit $?"
+timeout 400 python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || echo "bench default exit $?"
 for c in cfg1 cfg3 cfg4; do
-    timeout 400 python3 bench.py --config $c --no-extras > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || echo "bench $c exit $?"
+    timeout 400 python3 bench.py --full --config $c --no-extras > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || echo "bench $c exit $?"
 done
-timeout 400 python3 bench.py --config cfg5 --no-extras > "$OUT/bench_cfg5_shard.json" 2> "$OUT/bench_cfg5.err" || echo "bench cfg5 exit $?"
-timeout 400 python3 bench.py --config cfg2 --batch 16 --no-extras > "$OUT/bench_cfg2_b16.json" 2> "$OUT/bench_cfg2_b16.err" || echo "bench b16 exit $?"
-WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29544 timeout 300 python3 bench.py --force-dist --dist-backend nccl --no-extras > "$OUT/bench_nccl_world1.json" 2> "$OUT/bench_nccl_world1.err" || echo "nccl world1 exit $?"
+timeout 400 python3 bench.py --full --config cfg5 --no-extras > "$OUT/bench_cfg5_shard.json" 2> "$OUT/bench_cfg5.err" || echo "bench cfg5 exit $?"
+timeout 400 python3 bench.py --full --config cfg2 --batch 16 --no-extras > "$OUT/bench_cfg2_b16.json" 2> "$OUT/bench_cfg2_b16.err" || echo "bench b16 exit $?"
+WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29544 timeout 300 python3 bench.py --full --force-dist --dist-backend nccl --no-extras > "$OUT/bench_nccl_world1.json" 2> "$OUT/bench_nccl_world1.err" || echo "nccl world1 exit $?"
 timeout 600 python3 tools/long_ab.py > "$OUT/long_ab.txt" 2> /dev/null || echo "long_ab exit $?"
 timeout 600 python3 tools/f64long_ab.py 2> /dev/null | grep -v "Warning\|Forcing" > "$OUT/f64_long_ab.txt" || echo "f64long exit $?"
 timeout 300 python3 tools/opsbench.py 2> /dev/null | grep -v "Warning\|Forcing" > "$OUT/opsbench.txt" || echo "opsbench exit $?"

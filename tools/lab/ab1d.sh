@@ -1,6 +1,6 @@
 for rep in 1 2; do for v in a0 a1 cur; do
   if [ $v = cur ]; then unset PDWT_LIB_F32; else export PDWT_LIB_F32=$PWD/pypwt_amd/libalt_$v.so; fi
-  echo -n "$v: "; python3 bench.py --config cfg3 --steps 50 --warmup 10 --no-cpu-baseline --no-extras | python3 -c "
+  echo -n "$v: "; python3 bench.py --config cfg3 --steps 50 --warmup 10 --full --no-cpu-baseline --no-extras | python3 -c "
 import json,sys
 o=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%.2f us'%(o['ms_per_step']*1e3), ' '.join('%s %.1f'%(k['kernel'],k['avg_us']) for k in o['kernels']))"
