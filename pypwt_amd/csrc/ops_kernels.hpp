@@ -4,7 +4,8 @@
 // an operator that treats every band alike sweeps ONE contiguous range with
 // real4_t loads/stores (the reference launches one 16x16-thread kernel per level
 // or one cuBLAS-v1 call per band, pdwt/src/common.cu:219-371, wt.cu:368-416).
-// Padding is zero and every operator here maps 0 -> 0.
+// Padding is zero and every operator here maps 0 -> 0 (soft and linf with beta < 0 do not: the host zeroes the padding again
+// after such a sweep, plan.cpp: rezero_padding).
 //
 // Semantics (restated in oracle/pdwt_oracle.c):
 //   soft   x <- copysign(max(|x|-b,0), x)      pdwt/src/common.cu:13-52

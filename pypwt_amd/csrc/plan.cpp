@@ -1194,8 +1194,22 @@ int threshold_impl(pdwt_plan* p, int op, real_t beta, int do_app, int normalize,
     return threshold_sweep(p, op, beta, do_app, normalize, what);
 }
 
+// The sweeps below run over padded ranges and rely on "padding is zero and the operator maps 0 -> 0" (ops_kernels.hpp).  soft and
+// linf with a NEGATIVE beta do not: soft(0, b) = linf(0, b) = |b|.  (Accepted like the reference and pywt do: it grows every
+// coefficient by |b|.)  After such a sweep the at most 63 padding values behind every band are zeroed again, so that the norms
+// and every later sweep see the invariant; beta >= 0 takes the same launches as ever.
+int rezero_padding(pdwt_plan* p) {
+    const int B = p->batch;
+    for (size_t k = 0; k < p->bands.size(); k++) {
+        const long long n = p->bands[k].elems(B), pad = pad64(n) - n;
+        if (pad > 0) HIP_TRY(hipMemsetAsync(p->arena + p->bands[k].off + n, 0, (size_t)pad * sizeof(real_t), p->stream));
+    }
+    return PDWT_OK;
+}
+
 int threshold_sweep(pdwt_plan* p, int op, real_t beta, int do_app, int normalize, const char* what) {
     const int L = p->info.nlevels, B = p->batch;
+    const bool dirties_padding = (op == EW_SOFT || op == EW_LINF) && beta < real_t(0);
     if (do_app) {
         Stamp st(p, what);
         HIP_TRY(launch_ew(op, p->band(0), pad64(p->bands[0].elems(B)), app_beta(beta, L, normalize), p->stream));
@@ -1215,6 +1229,7 @@ int threshold_sweep(pdwt_plan* p, int op, real_t beta, int do_app, int normalize
             HIP_TRY(launch_ew(op, p->arena + first, last - first, beta, p->stream));
         }
     }
+    if (dirties_padding) return rezero_padding(p);
     return PDWT_OK;
 }
 
@@ -1493,6 +1508,15 @@ int pdwt_soft_threshold_norms_async(pdwt_handle h, real_t beta, int do_app, int 
         return fail(PDWT_ERR_STATE, "soft_threshold: cannot threshold coefficients, as they were modified by inverse()");
     const int rc0 = materialize_pending(h);  // an earlier pending threshold composes: apply it first
     if (rc0 != PDWT_OK) return rc0;
+    if (beta < real_t(0)) {
+        // soft(0, beta) = |beta|: the one-sweep form would count the padding in and leave it dirty (see rezero_padding); this rare
+        // case runs as the threshold and then the norms
+        const int rc = threshold_sweep(h, EW_SOFT, beta, do_app, normalize, "soft_threshold");
+        if (rc != PDWT_OK) return rc;
+        Stamp st(h, "norms");
+        HIP_TRY(launch_norms(h->arena, h->coeff_elems, h->d_red, d_out2 ? d_out2 : h->d_red, h->stream));
+        return PDWT_OK;
+    }
     const bool defer = !do_app && beta >= 0.f && can_defer_soft(h);
     if (defer) {
         h->pend_soft = true;
