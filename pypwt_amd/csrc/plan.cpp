@@ -1460,7 +1460,10 @@ int pdwt_circshift(pdwt_handle h, int sr, int sc, int inplace) {
 static int norms_impl(pdwt_handle h, double out[2]) {
     DeviceGuard guard(h->device);
     {
-        const int rc0 = materialize_pending(h);
+        // the sums are over what a reader of the coefficients would see: a deferred threshold is applied, and one that the fused
+        // inverse consumed on the fly is written back (norm1() after soft_threshold(); inverse() is the objective of an ISTA step)
+        int rc0 = materialize_pending(h);
+        if (rc0 == PDWT_OK) rc0 = materialize_consumed(h);
         if (rc0 != PDWT_OK) return rc0;
     }
     {
@@ -1484,7 +1487,8 @@ static int norms_impl(pdwt_handle h, double out[2]) {
 int pdwt_norms_async(pdwt_handle h, double* d_out2) {
     CHECK_HANDLE(h);
     DeviceGuard guard(h->device);
-    const int rc0 = materialize_pending(h);
+    int rc0 = materialize_pending(h);
+    if (rc0 == PDWT_OK) rc0 = materialize_consumed(h);  // see norms_impl
     if (rc0 != PDWT_OK) return rc0;
     Stamp st(h, "norms");
     HIP_TRY(launch_norms(h->arena, h->coeff_elems, h->d_red, d_out2 ? d_out2 : h->d_red, h->stream));

@@ -1,0 +1,216 @@
+"""The eager plan model (tests/plan_model.py) pinned to the CPU oracle, and the conditions on the call sequences that
+tests/test_gpu_sequences.py runs on the GPU, checked by running generator + model here, without one.
+
+The conditions are on the INPUTS of the GPU test: if a seed violates one, the generator changes, not the cap."""
+from collections import Counter
+
+import numpy as np
+import pytest
+
+import ops_ref
+import plan_model as pm
+from oracle import oracle
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _oracle():
+    oracle.build()
+
+
+def spec_of(name):
+    return [p for p in pm.PLANS if p.name == name][0]
+
+
+# ------------------------------------------------------------------------------------------- the model against the oracle alone
+@pytest.mark.parametrize("name", ["swt2-haar-64x96-L3", "dwt2-db4-256x256-L4", "dwt1-sym8-3x4096-L5", "swt1-db2-1x100-L2"])
+def test_model_agrees_with_the_oracle_on_a_fixed_sequence(name):
+    s = spec_of(name)
+    x = s.image(7)
+    m = pm.PlanModel(s, x)
+    kw = dict(ndim=s.ndim, do_swt=s.swt)
+    assert m.forward() == 0 and m.state == pm.FORWARD
+    ref = oracle.forward(x[0], s.wname, s.levels, **kw)
+    for g, r in zip(m.bands, ref):
+        assert np.array_equal(g[0], r)
+    for op, beta, do_app, norm in (("soft", 12.0, 0, 1), ("hard", 5.0, 1, 0), ("soft", -1.5, 1, 1)):
+        assert getattr(m, op + "_threshold")(beta, do_app, norm) == 0 and m.state == pm.FORWARD
+        ref = oracle.threshold(ref, s.shape, s.levels, op, beta, do_app, norm, **kw)
+        for k, (g, r) in enumerate(zip(m.bands, ref)):
+            assert ops_ref.same_bits(g[0], r), (op, k)
+    assert m.shrink(0.25, 1) == 0
+    ref = oracle.shrink(ref, s.shape, s.levels, 0.25, 1, **kw)
+    for g, r in zip(m.bands, ref):
+        assert ops_ref.same_bits(g[0], r)
+    n1, n2 = oracle.norms(ref, s.shape, s.levels, **kw)  # the oracle sums in float32
+    assert abs(m.norm1()[1] - n1) <= 1e-4 * n1 and abs(m.norm2sq()[1] - n2) <= 1e-4 * n2
+    assert m.norms_async() == 0 and m.norms_slot == m.norms()
+    before = [b.copy() for b in m.bands]
+    assert m.inverse() == 0 and m.state == pm.INVERSE
+    assert np.array_equal(m.image[0], oracle.inverse(ref, s.shape, s.wname, s.levels, **kw))
+    assert all(np.array_equal(a, b) for a, b in zip(before, m.bands)), "the inverse leaves the coefficients alone"
+
+
+def test_model_state_machine_and_return_values():
+    s = spec_of("swt2-db2-72x80-L3")
+    m = pm.PlanModel(s, s.image(3))
+    assert m.state == pm.INIT and m.get_coeff(1)[0] == 72 * 80  # legal before any forward: the zeroed arena
+    m.forward()
+    t = m.clone()
+    assert t.state == pm.FORWARD and t.bands[0] is not m.bands[0]
+    assert m.inverse() == 0 and m.inverse() == pm.ERR_STATE
+    for rc in (m.soft_threshold(1.0), m.hard_threshold(1.0), m.group_soft_threshold(1.0), m.shrink(1.0), m.proj_linf(1.0),
+               m.soft_threshold_norms(1.0)):
+        assert rc == pm.ERR_STATE
+    assert m.get_coeff(0)[0] == 0 and m.get_coeff_at(2, 0)[0] == 0 and m.get_coeff_region()[0] == 0
+    assert m.get_image()[0] == 72 * 80 and m.norm1()[0] == 0
+    assert m.add_wavelet(t, 1.0) == 1 and t.add_wavelet(m, 1.0) == 1
+    assert m.set_coeff(m.bands[3], 3) == 0 and m.state == pm.INVERSE
+    assert m.set_coeff(m.bands[0], 0) == 0 and m.state == pm.FORWARD  # re-armed
+    assert m.inverse() == 0 and m.set_image(s.image(4)) == 0 and m.state == pm.INIT
+    assert m.get_coeff_region()[0] == m.region()[1] == 10 * 72 * 80
+    assert m.add_wavelet(t, 0.5) == 0
+    m.set_filters_forward(s.banks()[1], "custom")
+    assert m.add_wavelet(t, 0.5) == -1
+    other = pm.PlanModel(spec_of("swt2-db2-64x64-L2-bound"), np.zeros((1, 64, 64)))
+    assert other.add_wavelet(t, 1.0) == -1  # the level count is compared first
+    # the region: bands back to back, each padded to 64 values
+    s = spec_of("swt2-db3-30x44-L2")
+    m = pm.PlanModel(s, s.image(1))
+    offs, total = m.region()
+    assert offs == [k * 1344 for k in range(7)] and total == 7 * 1344 and 30 * 44 == 1320
+    m.forward()
+    flat = m.flat_region()
+    assert not flat[1320:1344].any() and np.array_equal(flat[1344:1344 + 1320], m.bands[1].ravel())
+
+
+def test_model_circshift_and_cycle_spinning():
+    s = spec_of("swt2-sym4-64x64-L2-cycle")
+    x = s.image(9)
+    m = pm.PlanModel(s, x)
+    m.circshift(5, -7, 0)
+    assert np.array_equal(m.image, x)
+    m.circshift(5, -7, 1)
+    assert np.array_equal(m.image[0], oracle.circshift(x[0], 5, -7))
+    m.set_image(x)
+    m.forward(shift=(11, 50))
+    assert np.array_equal(m.image[0], oracle.circshift(x[0], 11, 50)) and m.shift == (11, 50)
+    assert np.array_equal(m.bands[2][0], oracle.forward(oracle.circshift(x[0], 11, 50), "sym4", 2, do_swt=1)[2])
+    m.inverse()
+    assert np.abs(m.image - x).max() < 7e-4
+    t = m.clone()
+    t.shift = (1, 2)
+    m.set_coeff(m.bands[0], 0)
+    t.set_coeff(t.bands[0], 0)
+    assert m.add_wavelet(t, 1.0) == -4
+
+
+def test_model_nonseparable_and_custom_banks():
+    s = spec_of("dwt2-nonsep-48x56-L2")
+    m = pm.PlanModel(s, s.image(2))
+    b = s.banks()[0]
+    m.set_filters_forward(b, "custom")
+    m.set_filters_inverse(b)
+    m.forward()
+    f = [t.ravel() for t in b[1]]
+    l1 = oracle.nonsep_forward_level(m.image[0], *f, s.hlen)
+    l2 = oracle.nonsep_forward_level(l1[0], *f, s.hlen)
+    for g, r in zip(m.bands, [l2[0]] + l1[1:] + l2[1:]):
+        assert np.array_equal(g[0], r)
+    m.inverse()
+    assert m.image.shape == (1, 48, 56) and np.isfinite(m.image).all()
+    s = spec_of("dwt2-custom9-64x68-L1")
+    m = pm.PlanModel(s, s.image(2))
+    assert m.dec[0] == 9 and m.forward() == 0 and m.bands[0].shape == (1, 32, 34)
+
+
+# ------------------------------------------------------------------------------------------- the generator's conditions
+@pytest.fixture(scope="module")
+def runs():
+    """every sequence of the GPU test through the model: {(plan, seed): [(op, situation before it, refused)]}"""
+    out = {}
+    for spec in pm.PLANS:
+        for seed in pm.SEEDS + (pm.CLASS_SEED,):
+            ops = pm.sequences()[(spec.name, seed)]
+            assert ops == pm.sequences()[(spec.name, seed)] and len(ops) == pm.LENGTH
+            rng = np.random.default_rng(seed)
+            m = pm.PlanModel(spec, spec.image(100 + seed))
+            if spec.custom or not spec.separable:
+                m.apply(("filt_fwd", 0))
+                m.apply(("filt_inv", 0))
+            m.forward(shift=(3, 5))
+            twin = m.clone()
+            sit, custom, rows = pm.Situation(), False, []
+            for op in ops:
+                before = sit.name()
+                rc, _ = m.apply(op, twin=twin, shift=tuple(int(v) for v in rng.integers(0, 60, 2)))
+                no = pm.refused(op, rc)
+                if not spec.cycle:  # (a cycle-spinning plan's add_wavelet also depends on the shifts the library draws)
+                    assert no == sit.would_refuse(op[0], custom), (spec, seed, op)
+                sit.step(op, custom)
+                if op[0] == "filt_fwd":
+                    custom = pm.bank_name(spec, op[1]) != pm.bank_name(spec, 0)
+                assert (sit.state == m.state) or no, (spec, seed, op)
+                rows.append((op, before, no))
+            out[(spec.name, seed)] = rows
+    return out
+
+
+def test_sequences_are_deterministic_and_complete():
+    assert len(pm.sequences()) == len(pm.PLANS) * 5
+    spec = pm.PLANS[0]
+    assert pm.generate(spec, 1) == pm.generate(spec, 1) and pm.generate(spec, 1) != pm.generate(spec, 2)
+    for (name, seed), ops in pm.sequences().items():
+        kinds = pm.REFERENCE_KINDS if seed == pm.CLASS_SEED else pm.KINDS
+        assert all(op[0] in kinds for op in ops)
+    assert "run_ops(spec, ops)" in pm.as_python(spec, 1, pm.sequences()[(spec.name, 1)], 3)
+
+
+def test_every_operation_kind_occurs_at_least_ten_times(runs):
+    n = Counter(op[0] for (name, seed), rows in runs.items() if seed != pm.CLASS_SEED for op, _, _ in rows)
+    assert all(n[k] >= 10 for k in pm.KINDS), sorted(n.items(), key=lambda t: t[1])[:5]
+    n = Counter(op[0] for (name, seed), rows in runs.items() if seed == pm.CLASS_SEED for op, _, _ in rows)
+    assert all(n[k] >= 10 for k in pm.REFERENCE_KINDS), sorted(n.items(), key=lambda t: t[1])[:5]
+
+
+def test_every_call_follows_every_lazy_situation_at_least_twice(runs):
+    """on the plans that defer (plan.cpp: can_defer_soft), through the C ABI"""
+    n = Counter()
+    for (name, seed), rows in runs.items():
+        if spec_of(name).defers and seed != pm.CLASS_SEED:
+            n.update((before, op[0]) for op, before, _ in rows)
+    missing = [(s, k, n[(s, k)]) for s in pm.SITUATIONS for k in pm.KINDS if n[(s, k)] < 2]
+    assert not missing, missing
+    assert sum(1 for p in pm.PLANS if p.defers) >= 10
+
+
+def test_refusals_are_capped_and_transforms_run(runs):
+    for (name, seed), rows in runs.items():
+        no = sum(1 for _, _, r in rows if r)
+        if not spec_of(name).cycle:
+            assert no <= 0.25 * len(rows), (name, seed, no)
+        for kind in ("forward", "inverse"):
+            assert sum(1 for op, _, r in rows if op[0] == kind and not r) >= 3, (name, seed, kind)
+
+
+def test_betas_matter():
+    """0, below, inside and above the details' magnitudes, a negative one; normalize and do_app both ways"""
+    seen, flags = Counter(), Counter()
+    for ops in pm.sequences().values():
+        for op in ops:
+            if op[0] in ("soft", "hard", "group", "soft_norms"):
+                seen[[k for k, v in pm.BETAS.items() if v == op[1]][0]] += 1
+                flags[("app", op[2])] += 1
+                flags[("normalize", op[3])] += 1
+    assert all(seen[k] >= 10 for k in pm.BETAS), seen
+    assert all(flags[(f, v)] >= 10 for f in ("app", "normalize") for v in (0, 1)), flags
+    for spec in pm.PLANS:
+        if spec.batch > 3:
+            continue
+        m = pm.PlanModel(spec, spec.image(101))
+        if spec.custom or not spec.separable:
+            m.apply(("filt_fwd", 0))
+        m.forward()
+        d = np.abs(np.concatenate([b.ravel() for b in m.bands[1:]]))
+        assert pm.BETAS["above"] > d.max() and pm.BETAS["negative"] < 0 == pm.BETAS["zero"], spec
+        assert 0.02 <= float((d > pm.BETAS["inside"]).mean()) <= 0.98, (spec, float((d > pm.BETAS["inside"]).mean()))
+        assert float((d > pm.BETAS["below"]).mean()) >= 0.99, spec
