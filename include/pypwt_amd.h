@@ -130,6 +130,45 @@ int pdwt_norm2sq(pdwt_handle h, pdwt_real* out); /* wt.cu:368-393 (1D bug at :38
 int pdwt_norms_async(pdwt_handle h, double* d_out2);
 int pdwt_norms_slot(pdwt_handle h, double** d_ptr); /* device address of the plan's own result slot (valid while the plan lives) */
 int pdwt_soft_threshold_norms_async(pdwt_handle h, pdwt_real beta, int do_thresh_appcoeffs, int normalize, double* d_out2);
+/* ---- NEW: adaptive denoising on the device (no reference counterpart: the reference's thresholds take ONE beta for all bands,
+ * wt.cu:308-325; the recipes are those of skimage.restoration.denoise_wavelet).  The threshold is picked from the data without
+ * moving a coefficient to the host: every call is enqueued on the plan's stream, does not wait for it, and leaves its results
+ * in device memory.  "Band" is the coefficient index `num`; "image" is an image of a batched plan (the rows of a batched 1D
+ * plan are pooled, as in every other operator).  The NOISE BAND is the finest diagonal band in 2D (num 3) and the finest
+ * detail band in 1D (num 1).  The small device workspace behind these calls is allocated by the first of them, so a plan
+ * that never calls them keeps its footprint.
+ *   pdwt_band_stats_async      {sum |c|, sum c^2} as two doubles for every (band, image), layout [nbands][batch][2], into
+ *                              d_out (device memory) or the plan's own slot when NULL.  One read-only sweep, fp64
+ *                              accumulation in a fixed order: bitwise reproducible from call to call.
+ *   pdwt_estimate_sigma_async  sigma[image] = median(|c|) / 0.6744897501960817 over the noise band, [batch] doubles into d_out
+ *                              or the plan's own slot.  The median is EXACT (a radix select on the bit pattern of |c|): the
+ *                              middle element of the sorted magnitudes, or the mean in double of the two middle ones; with
+ *                              skip_zeros exact zeros (-0.0 too) do not count; NaNs sort behind +inf; no element left: 0.
+ *   pdwt_threshold_bands       soft (op 0) or hard (op 1) threshold, bit for bit pdwt_soft_threshold's / pdwt_hard_threshold's
+ *                              arithmetic, with a threshold of its own per (band, image): table[nbands][batch] of pdwt_real in
+ *                              host memory (copied on the stream through a pinned buffer) or, table_on_device != 0, in device
+ *                              memory (read when the sweep runs).  A NaN entry leaves that band of that image untouched.  ONE
+ *                              launch over all bands; a negative entry is accepted as a negative beta is.
+ *   pdwt_denoise_async         the recipe: sigma (host memory: nsigma = 1 value for all images or nsigma = batch values; NULL =
+ *                              pdwt_estimate_sigma_async), the sums, a table kernel, pdwt_threshold_bands on that table --
+ *                              nothing waits for the host in between.
+ *                                PDWT_DENOISE_BAYES  T[b][i] = var / sqrt(max(sumsq[b][i] / n_b - var, eps)), var = sigma[i]^2,
+ *                                                    eps the machine epsilon of pdwt_real, n_b the elements of band b per image
+ *                                PDWT_DENOISE_VISU   T[b][i] = sigma[i] sqrt(2 ln(Nr Nc))
+ *                              computed in double and rounded once; T[0][i] (the approximation) = NaN.
+ *   pdwt_adaptive_slots        device addresses of the plan's own slots (any argument may be NULL): sums [nbands][batch][2],
+ *                              sigma [batch], the table of the last pdwt_denoise_async [nbands][batch]; valid while the plan
+ *                              lives (read them with pdwt_copy).
+ * State rules: the two read-only calls take what pdwt_norms_async takes; pdwt_threshold_bands and pdwt_denoise_async follow
+ * pdwt_soft_threshold -- PDWT_ERR_STATE after pdwt_inverse, nothing done -- and, like it, do not change the plan's state.  A
+ * threshold that a 2D SWT plan has deferred into its inverse is applied first, so it is seen by the sums and the median and
+ * composes with the sweep; the sweep itself is always eager. */
+typedef enum pdwt_denoise_method { PDWT_DENOISE_BAYES = 0, PDWT_DENOISE_VISU = 1 } pdwt_denoise_method;
+int pdwt_band_stats_async(pdwt_handle h, double* d_out);
+int pdwt_estimate_sigma_async(pdwt_handle h, int skip_zeros, double* d_out);
+int pdwt_threshold_bands(pdwt_handle h, int op, const pdwt_real* table, int table_on_device);
+int pdwt_denoise_async(pdwt_handle h, int method, int op, const double* sigma, int nsigma, int skip_zeros);
+int pdwt_adaptive_slots(pdwt_handle h, double** d_stats, double** d_sigma, pdwt_real** d_table);
 /* dst += alpha * src ; returns 0, or the reference's codes -1..-4 / +1 (wt.cu:622-655) */
 int pdwt_add_wavelet(pdwt_handle dst, pdwt_handle src, pdwt_real alpha);
 

@@ -35,6 +35,13 @@ cdef extern from "pypwt_amd.h":
     int pdwt_norms_async(pdwt_handle h, double* d_out2)
     int pdwt_norms_slot(pdwt_handle h, double** d_ptr)
     int pdwt_soft_threshold_norms_async(pdwt_handle h, float beta, int do_app, int normalize, double* d_out2)
+    # adaptive denoising on the device (no reference counterpart): per (band, image) sums, the exact median of the noise band,
+    # a threshold per (band, image) in one sweep, and the BayesShrink (method 0) / VisuShrink (1) recipe; results stay in device memory
+    int pdwt_band_stats_async(pdwt_handle h, double* d_out)                         # [nbands][batch][2]; NULL = the plan's slot
+    int pdwt_estimate_sigma_async(pdwt_handle h, int skip_zeros, double* d_out)     # [batch]; NULL = the plan's slot
+    int pdwt_threshold_bands(pdwt_handle h, int op, const float* table, int table_on_device)   # op 0 soft, 1 hard; NaN = untouched
+    int pdwt_denoise_async(pdwt_handle h, int method, int op, const double* sigma, int nsigma, int skip_zeros)
+    int pdwt_adaptive_slots(pdwt_handle h, double** d_stats, double** d_sigma, float** d_table)
     # data movement
     long long pdwt_get_image(pdwt_handle h, float* dst)                             # pypwt.pyx:52
     long long pdwt_get_coeff(pdwt_handle h, float* dst, int num)                    # pypwt.pyx:54

@@ -61,6 +61,11 @@ def signatures(real=C.c_float):
         "pdwt_norms_async": (C.c_int, [handle_t, C.c_void_p]),
         "pdwt_norms_slot": (C.c_int, [handle_t, C.POINTER(C.c_void_p)]),
         "pdwt_soft_threshold_norms_async": (C.c_int, [handle_t, real, C.c_int, C.c_int, C.c_void_p]),
+        "pdwt_band_stats_async": (C.c_int, [handle_t, C.c_void_p]),
+        "pdwt_estimate_sigma_async": (C.c_int, [handle_t, C.c_int, C.c_void_p]),
+        "pdwt_threshold_bands": (C.c_int, [handle_t, C.c_int, C.c_void_p, C.c_int]),
+        "pdwt_denoise_async": (C.c_int, [handle_t, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int]),
+        "pdwt_adaptive_slots": (C.c_int, [handle_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
         "pdwt_add_wavelet": (C.c_int, [handle_t, handle_t, real]),
         "pdwt_get_image": (C.c_longlong, [handle_t, C.c_void_p]),
         "pdwt_get_coeff": (C.c_longlong, [handle_t, C.c_void_p, C.c_int]),

@@ -15,6 +15,22 @@ namespace pdwt {
 // element-wise operator codes of launch_ew
 enum EwOp { EW_SOFT = 0, EW_HARD = 1, EW_LINF = 2, EW_SCALE = 3 };
 
+// threshold recipes of launch_denoise_table (== PDWT_DENOISE_BAYES / PDWT_DENOISE_VISU of pypwt_amd.h)
+enum DenoiseMethod { DENOISE_BAYES = 0, DENOISE_VISU = 1 };
+
+// The coefficient region cut into workgroup-sized pieces of ONE (band, image) pair each, for the operators that tell bands and
+// images apart (ops_kernels.hpp: band_piece).  Passed by value in the kernel-argument segment.  Band b holds `batch` images
+// of n[b] contiguous values from off[b] on; an image is cut into ceil(n[b] / chunk) pieces; the pieces of band b are the
+// workgroups blk[b] .. blk[b + 1] - 1, image by image.
+constexpr int kMaxBands = 96;
+struct BandTable {
+    int nbands, batch;
+    long long chunk;
+    long long off[kMaxBands];
+    long long n[kMaxBands];
+    int blk[kMaxBands + 1];
+};
+
 // Dispatch knobs that a level LAUNCH consults (pdwt_set_tuning).  A plan takes a snapshot when it is created and makes it
 // the calling thread's active set around its launches, so that two threads driving plans with different settings -- or a
 // third thread calling pdwt_set_tuning -- cannot change each other's kernel choice in mid-transform; with no active set
@@ -181,6 +197,20 @@ hipError_t launch_soft_norms(real_t* p, long long n, long long split, real_t b_l
                              double* scratch, int first_block, int max_blocks, int* blocks, hipStream_t s);
 hipError_t launch_norms_final(const double* scratch, int nblocks, double* out, hipStream_t s);
 int norms_max_blocks();
+// per (band, image) operators (ops_kernels.hpp).  partial: 2 * t.blk[t.nbands] doubles; stats: [nbands][batch][2] doubles;
+// d_table: [nbands][batch] thresholds in device memory, NaN = leave that pair alone; sigma: [batch] doubles (device)
+hipError_t launch_band_stats(const real_t* arena, const BandTable& t, double* partial, double* stats, hipStream_t s);
+hipError_t launch_threshold_bands(int op, real_t* arena, const BandTable& t, const real_t* d_table, hipStream_t s);
+hipError_t launch_denoise_table(const BandTable& t, const double* stats, const double* sigma, int method, double visu, real_t* d_table,
+                                hipStream_t s);
+// exact median of |c| per image by radix select (select_kernels.hpp): `passes` x (histogram sweep over band[batch][n], walk).
+// state: select_state_bytes(batch) bytes and hist: select_hist_bytes(batch) bytes of device memory, both zeroed ONCE by the
+// caller (the walks leave them zero again); the walk of the last pass writes sigma[image] = median / 0.6745
+int select_passes();
+size_t select_state_bytes(int batch);
+size_t select_hist_bytes(int batch);
+hipError_t launch_select_hist(const real_t* band, long long n, int batch, int pass, void* state, unsigned* hist, hipStream_t s);
+hipError_t launch_select_walk(long long n, int batch, int pass, int skip_zeros, void* state, unsigned* hist, double* sigma, hipStream_t s);
 hipError_t launch_circshift(const real_t* in, real_t* out, int batch, int Nr, int Nc, int sr, int sc, hipStream_t s);
 hipError_t launch_copy(const real_t* src, real_t* dst, long long n, hipStream_t s);  // 16-B grid-stride copy (n % 4 == 0)
 hipError_t launch_fill_hash(real_t* x, long long n, uint32_t seed, real_t scale, long long index_offset,

@@ -2,6 +2,7 @@
 #include "launch.hpp"
 #include "launch_util.hpp"
 #include "ops_kernels.hpp"
+#include "select_kernels.hpp"
 
 namespace pdwt {
 
@@ -70,6 +71,57 @@ hipError_t launch_norms_final(const double* scratch, int nblocks, double* out, h
     return hipGetLastError();
 }
 int norms_max_blocks() { return kNormsMaxBlocks; }
+
+hipError_t launch_band_stats(const real_t* arena, const BandTable& t, double* partial, double* stats, hipStream_t s) {
+    const int blocks = t.blk[t.nbands];
+    if (blocks < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(band_stats_partial_kernel, dim3(blocks), dim3(256), 0, s, arena, t, partial);
+    hipLaunchKernelGGL(band_stats_final_kernel, dim3(t.nbands * t.batch), dim3(64), 0, s, partial, t, stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_threshold_bands(int op, real_t* arena, const BandTable& t, const real_t* d_table, hipStream_t s) {
+    const int blocks = t.blk[t.nbands];
+    if (blocks < 1) return hipErrorInvalidValue;
+    switch (op) {
+        case EW_SOFT: hipLaunchKernelGGL((threshold_bands_kernel<EW_SOFT>), dim3(blocks), dim3(256), 0, s, arena, t, d_table); break;
+        case EW_HARD: hipLaunchKernelGGL((threshold_bands_kernel<EW_HARD>), dim3(blocks), dim3(256), 0, s, arena, t, d_table); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_table(const BandTable& t, const double* stats, const double* sigma, int method, double visu, real_t* d_table,
+                                hipStream_t s) {
+    hipLaunchKernelGGL(denoise_table_kernel, dim3(cdiv(t.nbands * t.batch, 256)), dim3(256), 0, s, t, stats, sigma, method, visu, d_table);
+    return hipGetLastError();
+}
+
+int select_passes() { return kSelectPasses; }
+size_t select_state_bytes(int batch) { return (size_t)batch * sizeof(SelectState); }
+size_t select_hist_bytes(int batch) { return (size_t)batch * kSelectMaxBins * sizeof(unsigned); }
+
+// pieces of an image of n values for the histogram sweep: about 1024 workgroups of 1024 threads over the whole band, 8192
+// values at least each (a workgroup zeroes and flushes a 32-KiB LDS histogram: short pieces would spend their time there)
+static long long select_chunk(long long n, int batch) {
+    long long per_image = 1024 / batch;
+    if (per_image < 1) per_image = 1;
+    long long chunk = cdivll(cdivll(n, per_image), 1024) * 1024;
+    return chunk < 8192 ? 8192 : chunk;
+}
+
+hipError_t launch_select_hist(const real_t* band, long long n, int batch, int pass, void* state, unsigned* hist, hipStream_t s) {
+    if (n < 1 || batch < 1 || batch > 65535 || pass < 0 || pass >= kSelectPasses) return hipErrorInvalidValue;
+    const long long chunk = select_chunk(n, batch);
+    hipLaunchKernelGGL(select_hist_kernel, dim3((unsigned)cdivll(n, chunk), batch), dim3(kSelectHistThreads), 0, s, band, n, chunk, pass,
+                       static_cast<SelectState*>(state), hist);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_walk(long long n, int batch, int pass, int skip_zeros, void* state, unsigned* hist, double* sigma, hipStream_t s) {
+    hipLaunchKernelGGL(select_walk_kernel, dim3(batch), dim3(256), 0, s, pass, n, skip_zeros, static_cast<SelectState*>(state), hist, sigma);
+    return hipGetLastError();
+}
 
 hipError_t launch_circshift(const real_t* in, real_t* out, int batch, int Nr, int Nc, int sr, int sc,
                             hipStream_t s) {

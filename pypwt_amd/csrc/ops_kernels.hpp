@@ -16,10 +16,17 @@
 //   axpy   dst += alpha*src                     pdwt/src/common.cu:499-526
 //   norms  sum|x|, sum x^2                      pdwt/src/wt.cu:368-416
 //   circshift                                   pdwt/src/common.cu:202-211
+//
+// Per (band, image) operators (no reference counterpart; the recipes are skimage.restoration.denoise_wavelet's):
+//   band_stats       sum|x|, sum x^2 of every image of every band
+//   threshold_bands  soft / hard with a threshold of its own per (band, image)
+//   denoise_table    BayesShrink / VisuShrink thresholds out of those sums and a noise level per image
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "launch.hpp"
 
@@ -177,6 +184,132 @@ __global__ void __launch_bounds__(256) norms_final_kernel(const double* __restri
         out[0] = part[0][0] + part[0][1] + part[0][2] + part[0][3];
         out[1] = part[1][0] + part[1][1] + part[1][2] + part[1][3];
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Operators that tell bands and images apart.  A (band, image) pair is n contiguous values at off[band] + image * n; n is
+// not a multiple of 4 in general (61 x 59 planes, batch 3), so the pairs do not start on 16-B boundaries.  The sweep is cut
+// into workgroup-sized pieces of ONE pair each (BandTable, launch.hpp): a piece reads single values up to the first whole
+// 16-B group, whole groups, and single values behind the last one -- the padding behind a band is never touched.
+
+// [a, e) of p, in elements from a 16-B aligned base (T = real_t or const real_t)
+template <typename T, typename FS, typename FV>
+__device__ __forceinline__ void sweep_range(T* __restrict__ p, long long a, long long e, FS one, FV four) {
+    typedef typename std::conditional<std::is_const<T>::value, const real4_t, real4_t>::type T4;
+    long long a4 = (a + 3) & ~3LL, e4 = e & ~3LL;
+    if (a4 > e) a4 = e;
+    if (e4 < a4) e4 = a4;
+    if ((long long)threadIdx.x < a4 - a) one(p[a + threadIdx.x]);
+    if ((long long)threadIdx.x < e - e4) one(p[e4 + threadIdx.x]);
+    T4* p4 = reinterpret_cast<T4*>(p);
+    for (long long i = a4 / 4 + threadIdx.x; i < e4 / 4; i += blockDim.x) four(p4[i]);
+}
+
+// workgroup `blk` of a per-pair sweep: its band, its image and its piece [*a, *e) of the arena
+__device__ __forceinline__ void band_piece(const BandTable& t, int blk, int* band, int* img, long long* a, long long* e) {
+    int b = 0;
+    while (b + 1 < t.nbands && blk >= t.blk[b + 1]) b++;
+    const long long n = t.n[b], slices = (n + t.chunk - 1) / t.chunk;
+    const long long r = blk - t.blk[b], i = r / slices, s = r - i * slices;
+    const long long first = t.off[b] + i * n, lo = first + s * t.chunk;
+    *band = b;
+    *img = (int)i;
+    *a = lo;
+    *e = lo + t.chunk < first + n ? lo + t.chunk : first + n;
+}
+
+// partial[2 blk], [2 blk + 1] = sum |x|, sum x^2 over the workgroup's piece (fp64, fixed order: wave shuffles, one LDS step)
+__global__ void __launch_bounds__(256) band_stats_partial_kernel(const real_t* __restrict__ arena, BandTable t, double* __restrict__ partial) {
+    int band, img;
+    long long a, e;
+    band_piece(t, blockIdx.x, &band, &img, &a, &e);
+    double s1 = 0.0, s2 = 0.0;
+    sweep_range(arena, a, e,
+                [&](const real_t& x) {
+                    s1 += (double)fabs(x);
+                    s2 += (double)x * x;
+                },
+                [&](const real4_t& v) {
+                    s1 += (double)fabs(v.x) + (double)fabs(v.y) + (double)fabs(v.z) + (double)fabs(v.w);
+                    s2 += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+                });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s1 += __shfl_down(s1, off, 64);
+        s2 += __shfl_down(s2, off, 64);
+    }
+    __shared__ double part[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        part[0][wave] = s1;
+        part[1][wave] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+        partial[2 * blockIdx.x + 1] = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+    }
+}
+// one wavefront per (band, image): out[band][image][0..1] = the sums of its pieces, in a fixed order
+__global__ void __launch_bounds__(64) band_stats_final_kernel(const double* __restrict__ partial, BandTable t, double* __restrict__ out) {
+    const int band = blockIdx.x / t.batch, img = blockIdx.x - band * t.batch;
+    const long long slices = (t.n[band] + t.chunk - 1) / t.chunk;
+    const double* p = partial + 2 * ((long long)t.blk[band] + (long long)img * slices);
+    double s1 = 0.0, s2 = 0.0;
+    for (long long k = threadIdx.x; k < slices; k += 64) {
+        s1 += p[2 * k];
+        s2 += p[2 * k + 1];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s1 += __shfl_down(s1, off, 64);
+        s2 += __shfl_down(s2, off, 64);
+    }
+    if (threadIdx.x == 0) {
+        out[2 * blockIdx.x] = s1;
+        out[2 * blockIdx.x + 1] = s2;
+    }
+}
+
+// x <- op(x, table[band][image]) for every pair in ONE launch; a NaN entry leaves its pair untouched (and unread)
+template <int OP>
+__global__ void __launch_bounds__(256) threshold_bands_kernel(real_t* __restrict__ arena, BandTable t, const real_t* __restrict__ table) {
+    int band, img;
+    long long a, e;
+    band_piece(t, blockIdx.x, &band, &img, &a, &e);
+    const real_t b = table[(long long)band * t.batch + img];
+    if (b != b) return;
+    sweep_range(arena, a, e, [&](real_t& x) { x = ew_apply<OP>(x, b); },
+                [&](real4_t& r) {
+                    real4_t v = r;
+                    v.x = ew_apply<OP>(v.x, b);
+                    v.y = ew_apply<OP>(v.y, b);
+                    v.z = ew_apply<OP>(v.z, b);
+                    v.w = ew_apply<OP>(v.w, b);
+                    r = v;
+                });
+}
+
+// table[band][image] out of stats[band][image] = {sum |c|, sum c^2} and sigma[image] (skimage.restoration._denoise:
+// _bayes_thresh, _universal_thresh), in double, rounded once to real_t; band 0 (the approximation) gets NaN
+//   BayesShrink  var / sqrt(max(sumsq / n - var, eps)),  var = sigma^2, eps = the machine epsilon of real_t
+//   VisuShrink   sigma * visu, visu = sqrt(2 ln(Nr Nc)) from the host
+__global__ void __launch_bounds__(256) denoise_table_kernel(BandTable t, const double* __restrict__ stats, const double* __restrict__ sigma,
+                                                            int method, double visu, real_t* __restrict__ table) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= t.nbands * t.batch) return;
+    const int band = idx / t.batch, img = idx - band * t.batch;
+    double T;
+    if (band == 0) {
+        T = __builtin_nan("");
+    } else if (method == DENOISE_VISU) {
+        T = sigma[img] * visu;
+    } else {
+        const double var = sigma[img] * sigma[img], eps = sizeof(real_t) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16;
+        const double d = stats[2 * idx + 1] / (double)t.n[band] - var;
+        T = var / sqrt(d > eps ? d : eps);
+    }
+    table[idx] = (real_t)T;
 }
 
 // out[b][y][x] = in[b][(y - sr) mod Nr][(x - sc) mod Nc],  0 <= sr < Nr, 0 <= sc < Nc

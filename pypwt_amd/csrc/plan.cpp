@@ -1233,6 +1233,123 @@ int threshold_sweep(pdwt_plan* p, int op, real_t beta, int do_app, int normalize
     return PDWT_OK;
 }
 
+// ---------------------------------------------------------------- per-band operators (adaptive denoising)
+//
+// band_stats, estimate_sigma, threshold_bands and denoise tell bands and images apart.  Their device workspace -- sums,
+// noise levels, threshold table, partial sums, the select's state and histograms -- is one block allocated by the first of
+// them that is called.  The sweep geometry (BandTable) is fixed with the plan's layout: about 2048 workgroups over the whole
+// coefficient region for the threshold sweep (1024 for the sums, the grids of the whole-arena map and norms kernels), pieces of
+// at least 4096 values, every piece inside one (band, image).
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+int ensure_adaptive(pdwt_plan* p) {
+    if (p->adaptive) return PDWT_OK;
+    const int nb = (int)p->bands.size(), B = p->batch;
+    if (nb > kMaxBands) return fail(PDWT_ERR_UNSUPPORTED, "per-band operators take at most %d bands (this plan has %d)", kMaxBands, nb);
+    if (B > 65535) return fail(PDWT_ERR_UNSUPPORTED, "per-band operators take at most 65535 images (this plan has %d)", B);
+    AdaptiveWs* w = new AdaptiveWs();
+    long long blocks = 0;
+    for (int which = 0; which < 2; which++) {
+        BandTable& t = which ? w->bt_stats : w->bt;
+        t.nbands = nb;
+        t.batch = B;
+        t.chunk = cdivll(cdivll(p->coeff_elems, which ? 1024 : 2048), 1024) * 1024;
+        if (t.chunk < 4096) t.chunk = 4096;
+        long long n_blocks = 0;
+        for (int k = 0; k < nb; k++) {
+            t.off[k] = p->bands[k].off;
+            t.n[k] = (long long)p->bands[k].rows * p->bands[k].cols;
+            t.blk[k] = (int)n_blocks;
+            n_blocks += (long long)B * cdivll(t.n[k], t.chunk);
+            if (t.n[k] >= (1LL << 31) || n_blocks >= (1LL << 30)) {
+                delete w;
+                return fail(PDWT_ERR_UNSUPPORTED, "per-band operators: band %d is too large", k);
+            }
+        }
+        t.blk[nb] = (int)n_blocks;
+        if (which) blocks = n_blocks;
+    }
+    const size_t sz_stats = align256((size_t)2 * nb * B * sizeof(double)), sz_sigma = align256((size_t)B * sizeof(double)),
+                 sz_table = align256((size_t)nb * B * sizeof(real_t)), sz_part = align256((size_t)2 * blocks * sizeof(double)),
+                 sz_state = align256(select_state_bytes(B)), sz_hist = align256(select_hist_bytes(B));
+    hipError_t e = pool_alloc(p->device, &w->block, sz_stats + sz_sigma + sz_table + sz_part + sz_state + sz_hist, &w->bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(w->block, 0, sz_stats + sz_sigma + sz_table + sz_part + sz_state + sz_hist, p->stream);
+    if (e == hipSuccess) e = hipHostMalloc(&w->h_stage, (size_t)nb * B * sizeof(real_t) + (size_t)B * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&w->staged, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (w->block) pool_free(p->device, w->block, w->bytes);
+        if (w->h_stage) (void)hipHostFree(w->h_stage);
+        delete w;
+        return fail(PDWT_ERR_HIP, "workspace of the per-band operators: %s", hipGetErrorString(e));
+    }
+    char* base = static_cast<char*>(w->block);
+    w->stats = reinterpret_cast<double*>(base);
+    w->sigma = reinterpret_cast<double*>(base + sz_stats);
+    w->table = reinterpret_cast<real_t*>(base + sz_stats + sz_sigma);
+    w->partial = reinterpret_cast<double*>(base + sz_stats + sz_sigma + sz_table);
+    w->sel_state = base + sz_stats + sz_sigma + sz_table + sz_part;
+    w->sel_hist = reinterpret_cast<unsigned*>(base + sz_stats + sz_sigma + sz_table + sz_part + sz_state);
+    p->adaptive = w;
+    return PDWT_OK;
+}
+
+void free_adaptive(pdwt_plan* p) {
+    AdaptiveWs* w = p->adaptive;
+    if (!w) return;
+    pool_free(p->device, w->block, w->bytes);
+    if (w->h_stage) (void)hipHostFree(w->h_stage);
+    if (w->staged) (void)hipEventDestroy(w->staged);
+    delete w;
+    p->adaptive = nullptr;
+}
+
+// `bytes` of host data to device memory on the plan's stream through the pinned staging buffer (offset `at` inside it); the host
+// waits only if the previous upload out of the buffer has not left it yet
+int stage_upload(pdwt_plan* p, void* d_dst, const void* h_src, size_t bytes, size_t at) {
+    AdaptiveWs* w = p->adaptive;
+    HIP_TRY(hipEventSynchronize(w->staged));
+    memcpy(static_cast<char*>(w->h_stage) + at, h_src, bytes);
+    HIP_TRY(hipMemcpyAsync(d_dst, static_cast<char*>(w->h_stage) + at, bytes, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipEventRecord(w->staged, p->stream));
+    return PDWT_OK;
+}
+
+// the noise band: the finest diagonal band in 2D, the finest detail band in 1D
+int noise_band(const pdwt_plan* p) { return p->info.ndims == 2 ? 3 : 1; }
+
+int band_stats_impl(pdwt_plan* p, double* d_out) {
+    Stamp st(p, "band_stats");
+    HIP_TRY(launch_band_stats(p->arena, p->adaptive->bt_stats, p->adaptive->partial, d_out ? d_out : p->adaptive->stats, p->stream));
+    return PDWT_OK;
+}
+
+int estimate_sigma_impl(pdwt_plan* p, int skip_zeros, double* d_out) {
+    AdaptiveWs* w = p->adaptive;
+    const int num = noise_band(p), B = p->batch;
+    const long long n = w->bt.n[num];
+    for (int pass = 0; pass < select_passes(); pass++) {
+        char name[32];
+        {
+            snprintf(name, sizeof(name), "select_hist%d", pass);
+            Stamp st(p, name);
+            HIP_TRY(launch_select_hist(p->band(num), n, B, pass, w->sel_state, w->sel_hist, p->stream));
+        }
+        {
+            snprintf(name, sizeof(name), "select_walk%d", pass);
+            Stamp st(p, name);
+            HIP_TRY(launch_select_walk(n, B, pass, skip_zeros ? 1 : 0, w->sel_state, w->sel_hist, d_out ? d_out : w->sigma, p->stream));
+        }
+    }
+    return PDWT_OK;
+}
+
+int threshold_bands_impl(pdwt_plan* p, int op, const real_t* d_table) {
+    Stamp st(p, "threshold_bands");
+    HIP_TRY(launch_threshold_bands(op, p->arena, p->adaptive->bt, d_table, p->stream));
+    return PDWT_OK;
+}
+
 std::string info_text(pdwt_plan* p) {
     // same lines as Wavelets::print_informations (pdwt/src/wt.cu:511-550)
     char buf[1024];
@@ -1342,6 +1459,7 @@ int pdwt_destroy(pdwt_handle h) {
     pool_free(h->device, h->arena, h->arena_bytes);
     if (h->tmp) (void)hipFree(h->tmp);
     pool_free(h->device, h->d_red, h->d_red_bytes);
+    free_adaptive(h);
     if (h->h_red) (void)hipHostFree(h->h_red);
     if (h->d_f2d) (void)hipFree(h->d_f2d);
     if (h->chain_flags) (void)hipFree(h->chain_flags);
@@ -1552,6 +1670,92 @@ int pdwt_soft_threshold_norms_async(pdwt_handle h, real_t beta, int do_app, int 
         }
     }
     HIP_TRY(launch_norms_final(h->d_red, used, out, h->stream));
+    return PDWT_OK;
+}
+
+// ---------------------------------------------------------------- NEW: adaptive denoising (no reference counterpart)
+// The two read-only operators take what pdwt_norms_async takes: a deferred threshold is applied, one that the fused inverse
+// consumed on the fly is written back, and the sums / the median are those of what a reader of the coefficients would see.
+int pdwt_band_stats_async(pdwt_handle h, double* d_out) {
+    CHECK_HANDLE(h);
+    DeviceGuard guard(h->device);
+    int rc = materialize_pending(h);
+    if (rc == PDWT_OK) rc = materialize_consumed(h);
+    if (rc == PDWT_OK) rc = ensure_adaptive(h);
+    if (rc != PDWT_OK) return rc;
+    return band_stats_impl(h, d_out);
+}
+
+int pdwt_estimate_sigma_async(pdwt_handle h, int skip_zeros, double* d_out) {
+    CHECK_HANDLE(h);
+    DeviceGuard guard(h->device);
+    int rc = materialize_pending(h);
+    if (rc == PDWT_OK) rc = materialize_consumed(h);
+    if (rc == PDWT_OK) rc = ensure_adaptive(h);
+    if (rc != PDWT_OK) return rc;
+    return estimate_sigma_impl(h, skip_zeros, d_out);
+}
+
+// The two sweeps follow pdwt_soft_threshold (wt.cu:308-315): refused after inverse(), a deferred threshold composes (it is
+// applied first); the sweep itself is always eager.  Its pieces cover the bands' own values only, so a negative entry
+// (soft(0, b) = |b|) cannot dirty the zero padding behind a band.
+int pdwt_threshold_bands(pdwt_handle h, int op, const real_t* table, int table_on_device) {
+    CHECK_HANDLE(h);
+    if (!table) return fail(PDWT_ERR_ARG, "threshold_bands: null table");
+    if (op != EW_SOFT && op != EW_HARD) return fail(PDWT_ERR_ARG, "threshold_bands: op must be 0 (soft) or 1 (hard)");
+    if (h->state == PDWT_INVERSE)
+        return fail(PDWT_ERR_STATE, "threshold_bands: cannot threshold coefficients, as they were modified by inverse()");
+    DeviceGuard guard(h->device);
+    int rc = materialize_pending(h);
+    if (rc == PDWT_OK) rc = ensure_adaptive(h);
+    if (rc != PDWT_OK) return rc;
+    AdaptiveWs* w = h->adaptive;
+    if (!table_on_device) {
+        rc = stage_upload(h, w->table, table, (size_t)w->bt.nbands * w->bt.batch * sizeof(real_t), 0);
+        if (rc != PDWT_OK) return rc;
+        table = w->table;
+    }
+    return threshold_bands_impl(h, op, table);
+}
+
+int pdwt_denoise_async(pdwt_handle h, int method, int op, const double* sigma, int nsigma, int skip_zeros) {
+    CHECK_HANDLE(h);
+    if (method != PDWT_DENOISE_BAYES && method != PDWT_DENOISE_VISU) return fail(PDWT_ERR_ARG, "denoise: unknown method %d", method);
+    if (op != EW_SOFT && op != EW_HARD) return fail(PDWT_ERR_ARG, "denoise: op must be 0 (soft) or 1 (hard)");
+    if (sigma && nsigma != 1 && nsigma != h->batch)
+        return fail(PDWT_ERR_ARG, "denoise: %d noise levels for %d images (one, or one per image)", nsigma, h->batch);
+    if (h->state == PDWT_INVERSE)
+        return fail(PDWT_ERR_STATE, "denoise: cannot threshold coefficients, as they were modified by inverse()");
+    DeviceGuard guard(h->device);
+    int rc = materialize_pending(h);
+    if (rc == PDWT_OK) rc = ensure_adaptive(h);
+    if (rc != PDWT_OK) return rc;
+    AdaptiveWs* w = h->adaptive;
+    if (sigma) {
+        std::vector<double> per((size_t)h->batch);
+        for (int i = 0; i < h->batch; i++) per[i] = sigma[nsigma == 1 ? 0 : i];
+        rc = stage_upload(h, w->sigma, per.data(), per.size() * sizeof(double), (size_t)w->bt.nbands * w->bt.batch * sizeof(real_t));
+    } else {
+        rc = estimate_sigma_impl(h, skip_zeros, nullptr);
+    }
+    if (rc == PDWT_OK && method == PDWT_DENOISE_BAYES) rc = band_stats_impl(h, nullptr);
+    if (rc != PDWT_OK) return rc;
+    {
+        Stamp st(h, "denoise_table");
+        const double visu = sqrt(2.0 * log((double)h->info.Nr * (double)h->info.Nc));
+        HIP_TRY(launch_denoise_table(w->bt, w->stats, w->sigma, method, visu, w->table, h->stream));
+    }
+    return threshold_bands_impl(h, op, w->table);
+}
+
+int pdwt_adaptive_slots(pdwt_handle h, double** d_stats, double** d_sigma, real_t** d_table) {
+    CHECK_HANDLE(h);
+    DeviceGuard guard(h->device);
+    const int rc = ensure_adaptive(h);
+    if (rc != PDWT_OK) return rc;
+    if (d_stats) *d_stats = h->adaptive->stats;
+    if (d_sigma) *d_sigma = h->adaptive->sigma;
+    if (d_table) *d_table = h->adaptive->table;
     return PDWT_OK;
 }
 

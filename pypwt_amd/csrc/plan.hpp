@@ -48,6 +48,24 @@ struct KernelStamp {
     char family[16];  // which of a step's alternative kernels ran (launch.hpp: note_family); "" when the step has only one
 };
 
+// Device workspace of the per-band operators (band_stats, estimate_sigma, threshold_bands, denoise): ONE block, allocated
+// by the first of them that is called, so that plans that never call them keep their footprint (plan.cpp: ensure_adaptive)
+struct AdaptiveWs {
+    void* block = nullptr;
+    size_t bytes = 0;
+    double* stats = nullptr;    // [nbands][batch][2]: sum |c|, sum c^2
+    double* sigma = nullptr;    // [batch]
+    real_t* table = nullptr;    // [nbands][batch] thresholds of the last denoise / host table of threshold_bands
+    double* partial = nullptr;  // per-workgroup partial sums of band_stats
+    void* sel_state = nullptr;  // radix select: per-image state and histogram (select_kernels.hpp)
+    unsigned* sel_hist = nullptr;
+    BandTable bt{};        // the sweep of threshold_bands: about 2048 pieces, the grid of the whole-arena maps
+    BandTable bt_stats{};  // ... of band_stats: about 1024, the grid of the whole-arena norms
+    // pinned host staging of a table / of noise levels the caller passes in host memory, and the event behind its last upload
+    void* h_stage = nullptr;
+    hipEvent_t staged = nullptr;
+};
+
 }  // namespace pdwt
 
 struct pdwt_plan {
@@ -104,6 +122,8 @@ struct pdwt_plan {
 
     bool timing = false;
     std::vector<pdwt::KernelStamp> stamps;
+
+    pdwt::AdaptiveWs* adaptive = nullptr;  // lazily allocated (plan.cpp: ensure_adaptive)
 
     real_t* image_ext = nullptr;  // pdwt_bind_image: the image lives in memory the caller owns (another plan's band, say)
     real_t* image() const { return image_ext ? image_ext : arena + image_off; }

@@ -97,7 +97,143 @@ class DeviceArray(object):
         return int(np.prod(self.shape)) * self.dtype.itemsize
 
 
-class Wavelets(object):
+def _read_device(lib, h, addr, shape, dtype):
+    """A plan-owned device buffer copied to the host: a blocking device-to-host pdwt_copy on the plan's stream."""
+    host = np.zeros(shape, dtype=dtype)
+    count = host.nbytes // C.sizeof(lib.pdwt_real)  # pdwt_copy counts elements of pdwt_real
+    check(lib.pdwt_copy(h, host.ctypes.data_as(C.c_void_p), C.c_void_p(int(addr)), count, 2), "pdwt_copy", lib)
+    return host
+
+
+class _AdaptiveOps(object):
+    """NEW (no reference counterpart): the threshold picked from the data, on the device -- per (band, image) sums, the exact
+    median of the noise band, one threshold per (band, image) in one sweep, and the BayesShrink / VisuShrink recipes of
+    ``skimage.restoration.denoise_wavelet`` on top of them.  Shared by ``Wavelets`` (one image) and ``BatchedWavelets``; "band" is
+    the index of ``coeff_only``, the noise band is D1 (band 3 in 2D, band 1 in 1D).  Everything is enqueued on the plan's stream
+    and not waited for; results stay in device memory until a ``read_*`` / ``last_thresholds`` call copies them."""
+
+    _DENOISE_METHODS = {"bayesshrink": 0, "visushrink": 1}
+    _THRESHOLD_MODES = {"soft": 0, "hard": 1}
+
+    def _adaptive_dims(self):
+        info, b = PdwtInfo(), C.c_int()
+        check(self._lib.pdwt_get_info(self._h, C.byref(info), None, None, None, C.byref(b)), "", self._lib)
+        return (3 * info.nlevels + 1 if info.ndims == 2 else info.nlevels + 1), int(b.value)
+
+    def _adaptive_slots(self):
+        st, sg, tb = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self._lib.pdwt_adaptive_slots(self._h, C.byref(st), C.byref(sg), C.byref(tb)), "pdwt_adaptive_slots", self._lib)
+        return st.value, sg.value, tb.value
+
+    def _adaptive_view(self, ptr, shape, dtype):
+        return DeviceArray(self, ptr, shape, dtype, int(self._lib.pdwt_get_stream(self._h) or 0))
+
+    def _adaptive_out(self, out, count, which):
+        """(argument for the C call, view to return) of an optional caller-owned float64 device array."""
+        if out is None:
+            return C.c_void_p(None), None
+        dev = _device_array(out, np.float64)
+        if dev is None or int(np.prod(dev[1])) < count:
+            raise ValueError("%s: `out` must be a device array of %d float64" % (which, count))
+        return C.c_void_p(dev[0]), out
+
+    @staticmethod
+    def _adaptive_choice(table, name, what):
+        try:
+            return table[str(name).lower()]
+        except KeyError:
+            raise ValueError("unknown %s %r (expected one of %s)" % (what, name, ", ".join(sorted(table))))
+
+    def _refused(self, rc):
+        """The reference's rule for thresholds after inverse() (wt.cu:309-312): a warning, nothing done."""
+        if rc == _lib.ERR_STATE:
+            print("Warning: Wavelets(): " + _lib.last_error(self._lib))
+            return True
+        check(rc, "", self._lib)
+        return False
+
+    def band_stats(self, out=None):
+        """(sum |c|, sum c^2) of every image of every band as float64 ON THE DEVICE: a (nbands, batch, 2) device array -- ``out``
+        if given, else a view of the plan's own slot.  One read-only sweep; two calls give the same bits."""
+        nb, batch = self._adaptive_dims()
+        arg, view = self._adaptive_out(out, 2 * nb * batch, "band_stats")
+        check(self._lib.pdwt_band_stats_async(self._h, arg), "band_stats", self._lib)
+        return view if view is not None else self._adaptive_view(self._adaptive_slots()[0], (nb, batch, 2), np.float64)
+
+    def estimate_sigma(self, skip_zeros=True, out=None):
+        """The noise level of every image, sigma = median(|D1|) / 0.6745 (Donoho and Johnstone), as float64 ON THE DEVICE: a
+        (batch,) device array.  The median is exact; ``skip_zeros`` (default, as skimage does) leaves exact zeros out of it."""
+        nb, batch = self._adaptive_dims()
+        arg, view = self._adaptive_out(out, batch, "estimate_sigma")
+        check(self._lib.pdwt_estimate_sigma_async(self._h, 1 if skip_zeros else 0, arg), "estimate_sigma", self._lib)
+        return view if view is not None else self._adaptive_view(self._adaptive_slots()[1], (batch,), np.float64)
+
+    def read_band_stats(self, view=None):
+        """What ``band_stats`` left on the device, copied to the host (waits for the plan's stream): (nbands, batch, 2) float64."""
+        nb, batch = self._adaptive_dims()
+        addr = self._adaptive_slots()[0] if view is None else int(view.__cuda_array_interface__["data"][0])
+        return _read_device(self._lib, self._h, addr, (nb, batch, 2), np.float64)
+
+    def read_sigma(self, view=None):
+        """What ``estimate_sigma`` (or ``denoise``) left on the device, copied to the host: (batch,) float64."""
+        nb, batch = self._adaptive_dims()
+        addr = self._adaptive_slots()[1] if view is None else int(view.__cuda_array_interface__["data"][0])
+        return _read_device(self._lib, self._h, addr, (batch,), np.float64)
+
+    def threshold_bands(self, betas, mode="soft"):
+        """Soft or hard threshold with a threshold of its own per (band, image), in ONE sweep: ``betas`` is a (nbands, batch)
+        array of the instance's dtype -- a numpy array (a (nbands,) array is one row for all images) or any device-array holder
+        ``set_coeff`` accepts.  A NaN entry leaves that band of that image untouched (entry 0 is the approximation)."""
+        op = self._adaptive_choice(self._THRESHOLD_MODES, mode, "mode")
+        nb, batch = self._adaptive_dims()
+        dev = _device_array(betas, self._dtype)
+        if dev is not None:
+            if int(np.prod(dev[1])) != nb * batch:
+                raise ValueError("threshold_bands: expected %d thresholds (%d bands x %d images), got %d"
+                                 % (nb * batch, nb, batch, int(np.prod(dev[1]))))
+            if dev[2]:  # order the sweep after the table's producer, as set_coeff does
+                if dev[2][0] == "stream":
+                    check(self._lib.pdwt_wait_for_stream(self._h, C.c_void_p(dev[2][1])), "", self._lib)
+                else:
+                    owner = int(self._lib.pdwt_device_of_pointer(C.c_void_p(dev[0])))
+                    check(self._lib.pdwt_sync_producer(owner if owner >= 0 else self._lib.pdwt_device(self._h), None, 1), "", self._lib)
+            self._refused(self._lib.pdwt_threshold_bands(self._h, op, C.c_void_p(dev[0]), 1))
+            return
+        t = np.asarray(betas, dtype=self._dtype)
+        if t.shape == (nb,):
+            t = np.repeat(t[:, None], batch, axis=1)
+        if t.shape != (nb, batch):
+            raise ValueError("threshold_bands: expected thresholds of shape (%d,) or (%d, %d), got %s" % (nb, nb, batch, str(t.shape)))
+        t = np.ascontiguousarray(t)
+        self._refused(self._lib.pdwt_threshold_bands(self._h, op, _ptr(t), 0))
+
+    def denoise(self, method="BayesShrink", sigma=None, mode="soft", skip_zeros=True):
+        """Adaptive wavelet shrinkage of the current coefficients (run ``forward`` before and ``inverse`` after it).
+        ``method``: "BayesShrink" (a threshold per detail band, Chang, Yu and Vetterli; skimage's default) or "VisuShrink" (the
+        universal threshold sigma sqrt(2 ln N)); ``sigma``: the noise level, a number or one per image, None = ``estimate_sigma``;
+        ``mode``: "soft" or "hard".  Nothing goes through the host; ``last_thresholds`` shows what was applied."""
+        m = self._adaptive_choice(self._DENOISE_METHODS, method, "method")
+        op = self._adaptive_choice(self._THRESHOLD_MODES, mode, "mode")
+        if sigma is None:
+            arg, n = None, 0
+        else:
+            sg = np.ascontiguousarray(np.atleast_1d(np.asarray(sigma, dtype=np.float64)))
+            batch = self._adaptive_dims()[1]
+            if sg.ndim != 1 or sg.size not in (1, batch):
+                raise ValueError("denoise: sigma must be a number or %d numbers (one per image)" % batch)
+            arg, n = sg.ctypes.data_as(C.POINTER(C.c_double)), int(sg.size)
+        self._refused(self._lib.pdwt_denoise_async(self._h, m, op, arg, n, 1 if skip_zeros else 0))
+
+    def last_thresholds(self):
+        """(sigma, thresholds) of the last ``denoise``, copied to the host (waits for the plan's stream): sigma is (batch,)
+        float64, thresholds (nbands, batch) of the instance's dtype with NaN in row 0 (the approximation is left alone)."""
+        nb, batch = self._adaptive_dims()
+        _, sg, tb = self._adaptive_slots()
+        return (_read_device(self._lib, self._h, sg, (batch,), np.float64),
+                _read_device(self._lib, self._h, tb, (nb, batch), self._dtype))
+
+
+class Wavelets(_AdaptiveOps):
     """
     A wavelet-transform plan bound to one image (or one batch of rows) on the GPU: the drop-in for pycudwt's class of the
     same name (constructor signature, attributes and coefficient layout of src/pypwt.pyx:64-615).
@@ -548,7 +684,7 @@ class Wavelets64(Wavelets):
     _variant = "f64"
 
 
-class BatchedWavelets(object):
+class BatchedWavelets(_AdaptiveOps):
     """NEW (not in the reference): one plan over a batch of independent images [B][Nr][Nc].
 
     Every call (forward / inverse / soft_threshold) processes all B images in the same kernel

@@ -42,3 +42,57 @@ for shape, wname, L, swt in (((4096, 4096), "db4", 4, 0), ((2048, 2048), "haar",
     ):
         us = t(fn, W.synchronize)
         print("  %-22s %8.1f us  %7.0f GB/s" % (name, us, nbytes / us / 1e3))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The per (band, image) operators (band_stats, estimate_sigma, threshold_bands, denoise) next to the whole-arena sweeps that
+# move the same bytes, on the default config's plans (4096^2 db4 L4, batch 1 and 16) and the SWT config's (2048^2 haar L5).
+# Hash input: the detail bands are noise-like, which is what the first pass of the select has to cope with.
+from collections import defaultdict
+
+from pypwt_amd import BatchedWavelets
+
+for batch, N, wname, L, swt in ((1, 4096, "db4", 4, 0), (16, 4096, "db4", 4, 0), (1, 2048, "haar", 5, 1)):
+    B = BatchedWavelets(batch, N, N, wname, L, do_swt=swt)
+    B.fill_hash(1, 255.0)
+    B.forward()
+    n = batch * N * N
+    ncoef = n * ((3 * L + 1) if swt else 1)
+    ndet = ncoef - (n if swt else n // 4 ** L)
+    nnoise = n if swt else n // 4
+    print("# adaptive: %d x %d^2 %s L%d%s: %d coefficients, noise band %d" % (batch, N, wname, L, " swt" if swt else "", ncoef, nnoise))
+    table = np.full((B.nbands, batch), 1e-3, dtype=np.float32)
+    table[0] = np.nan
+    B.threshold_bands(table)                                        # host table once: it now sits in the plan's slot ...
+    dtab = B._adaptive_view(B._adaptive_slots()[2], table.shape, np.float32)   # ... and is read from there (no upload per call)
+    for name, fn, nbytes in (
+        ("hard_threshold", lambda: B._lib.pdwt_hard_threshold(B._h, 1e-3, 0, 0), 8 * ndet),
+        ("threshold_bands", lambda: B.threshold_bands(dtab), 8 * ndet),
+        ("threshold_bands(hard)", lambda: B.threshold_bands(dtab, "hard"), 8 * ndet),
+        ("norms_device", B.norms_device, 4 * ncoef),
+        ("band_stats", B.band_stats, 4 * ncoef),
+        ("estimate_sigma", B.estimate_sigma, 4 * nnoise * 3),
+        ("denoise(BayesShrink)", B.denoise, 4 * nnoise * 3 + 4 * ncoef + 8 * ndet),
+        ("denoise(sigma given)", lambda: B.denoise(sigma=1.0), 4 * ncoef + 8 * ndet),
+        ("fwd+soft+inv (parent)", lambda: (B.forward(), B.soft_threshold(1.0), B.inverse()), 0),
+        ("fwd+denoise+inv", lambda: (B.forward(), B.denoise(), B.inverse()), 0),
+    ):
+        B.forward()
+        us = t(fn, B.synchronize, 30)
+        print("  %-22s %8.1f us" % (name, us) + ("  %7.0f GB/s" % (nbytes / us / 1e3) if nbytes else ""))
+    # the select pass by pass (per-launch event timing: a few us of overhead per launch)
+    B.forward()
+    B.enable_kernel_timing(True)
+    B.reset_kernel_times()
+    for _ in range(20):
+        B.estimate_sigma()
+    B.synchronize()
+    acc = defaultdict(list)
+    for name, ms in B.kernel_times():
+        acc[name].append(ms * 1e3)
+    for name in sorted(acc):
+        us = float(np.median(acc[name]))
+        rate = "  %7.0f GB/s read" % (4 * nnoise / us / 1e3) if name.startswith("select_hist") else ""
+        print("  %-22s %8.1f us%s" % (name, us, rate))
+    B.enable_kernel_timing(False)
+    del B
