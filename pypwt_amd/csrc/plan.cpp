@@ -800,9 +800,9 @@ int fwd_level_2d(pdwt_plan* p, int l, bool run) {
 }
 
 // deferred soft_threshold: beta of level l's details (/ sqrt(2)^l when normalised)
-real_t pending_beta_of_level(const pdwt_plan* p, int l) {
-    real_t b = p->pend_beta;
-    if (p->pend_normalize > 0)
+real_t pending_beta_of_level(const LazyThreshold& t, int l) {
+    real_t b = t.beta;
+    if (t.normalize > 0)
         for (int i = 0; i < l; i++) b = (real_t)(b / 1.4142135623730951);
     return b;
 }
@@ -864,16 +864,16 @@ int inv_level_2d(pdwt_plan* p, int l, bool run) {
         a.bstride = (long long)Nr * Nc;
         a.hlen = hlen;
         a.soft_beta = 0.f;
-        if (p->pend_soft) a.soft_beta = pending_beta_of_level(p, l);
+        if (p->pending.on) a.soft_beta = pending_beta_of_level(p->pending, l);
         a.fb = p->rec;
         if (swt2_inv_stream_takes(a, B)) {  // row and column synthesis in one launch, streamed down strips (swt_invstream_kernels.hpp)
-            Stamp st(p, p->pend_soft ? "swt2_inv_stream+soft" : "swt2_inv_stream");
+            Stamp st(p, p->pending.on ? "swt2_inv_stream+soft" : "swt2_inv_stream");
             if (run) HIP_TRY(try_launch_swt2_inv_stream(a, B, p->stream));
             return PDWT_OK;
         }
         bool split = swt2_split_supported(hlen, Nr, Nc, f, true, (long long)B * Nr * Nc) && ensure_tmp(p, 2LL * Nr * Nc * B) == PDWT_OK;
         if (split) {  // a decline (hipErrorNotSupported) falls through to the other kernels, see fwd_level_2d
-            Stamp st(p, p->pend_soft ? "swt2_inv_split+soft" : "swt2_inv_split");
+            Stamp st(p, p->pending.on ? "swt2_inv_split+soft" : "swt2_inv_split");
             const hipError_t e = run ? launch_swt2_split(a, p->tmp, true, B, p->stream) : hipSuccess;
             if (e == hipErrorNotSupported) {
                 split = false;
@@ -883,7 +883,7 @@ int inv_level_2d(pdwt_plan* p, int l, bool run) {
             }
         }
         if (!split) {
-            Stamp st(p, p->pend_soft ? "swt2_inv_level+soft" : "swt2_inv_level");
+            Stamp st(p, p->pending.on ? "swt2_inv_level+soft" : "swt2_inv_level");
             if (run) HIP_TRY(launch_swt2_inv(a, B, p->stream));
         }
     }
@@ -1070,9 +1070,9 @@ int inverse_impl(pdwt_plan* p, int only = 0) {
             real_t* det[3 * kTailMaxLevelsHost] = {};
             for (int k = 0; k < 3 * s.K; k++) det[k] = p->band(1 + k);
             real_t beta[kTailMaxLevelsHost] = {};
-            if (p->pend_soft)  // deferred soft_threshold, applied as the details are staged (see inv_level_2d)
-                for (int k = 0; k < s.K; k++) beta[k] = pending_beta_of_level(p, 1 + k);
-            Stamp st(p, p->pend_soft ? "swt2_inv_tail+soft" : "swt2_inv_tail", &e);
+            if (p->pending.on)  // deferred soft_threshold, applied as the details are staged (see inv_level_2d)
+                for (int k = 0; k < s.K; k++) beta[k] = pending_beta_of_level(p->pending, 1 + k);
+            Stamp st(p, p->pending.on ? "swt2_inv_tail+soft" : "swt2_inv_tail", &e);
             if (!run) continue;
             e = launch_swt2_tail(approx_slot(p, s.K), det, approx_slot(p, 0), p->info.Nr, p->info.Nc, s.K, hlen, true, p->rec, beta, B,
                                  p->stream);
@@ -1094,9 +1094,9 @@ int inverse_impl(pdwt_plan* p, int only = 0) {
             real_t* det[9] = {};
             for (int k = 0; k < 3 * s.K; k++) det[k] = p->band(3 * (l - 1) + 1 + k);
             real_t beta[3] = {0, 0, 0};
-            if (p->pend_soft)  // deferred soft_threshold, applied as the details are loaded (see inv_level_2d)
-                for (int k = 0; k < s.K; k++) beta[k] = pending_beta_of_level(p, l + k);
-            Stamp st(p, p->pend_soft ? "swt2_inv_fused+soft" : "swt2_inv_fused", &e);
+            if (p->pending.on)  // deferred soft_threshold, applied as the details are loaded (see inv_level_2d)
+                for (int k = 0; k < s.K; k++) beta[k] = pending_beta_of_level(p->pending, l + k);
+            Stamp st(p, p->pending.on ? "swt2_inv_fused+soft" : "swt2_inv_fused", &e);
             if (!run) continue;
             e = launch_swt2_fused(approx_slot(p, l + s.K - 1), approx_slot(p, l - 1), det, p->info.Nr, p->info.Nc, l, s.K, true,
                                   p->info.hlen, p->rec, beta, B, p->stream);
@@ -1155,25 +1155,7 @@ real_t app_beta(real_t beta, int levels, int normalize) {
     return beta;
 }
 
-int threshold_impl(pdwt_plan* p, int op, real_t beta, int do_app, int normalize, const char* what);
 int threshold_sweep(pdwt_plan* p, int op, real_t beta, int do_app, int normalize, const char* what);
-
-// apply a deferred soft_threshold now (every consumer of the coefficients other than the fused SWT
-// inverse calls this first)
-int materialize_pending(pdwt_plan* p) {
-    if (!p->pend_soft) return PDWT_OK;
-    p->pend_soft = false;
-    return threshold_impl(p, EW_SOFT, p->pend_beta, 0, p->pend_normalize, "soft_threshold");
-}
-
-// A deferred threshold that the fused SWT inverse applied on the fly never reached the stored detail
-// bands.  Before they become observable again (set_coeff re-arming the inverse, a device pointer handed
-// out) it is applied to them, so that the result does not depend on whether the fused path was taken.
-int materialize_consumed(pdwt_plan* p) {
-    if (!p->soft_consumed) return PDWT_OK;
-    p->soft_consumed = false;
-    return threshold_sweep(p, EW_SOFT, p->consumed_beta, 0, p->consumed_normalize, "soft_threshold");
-}
 
 // can the inverse of this plan apply a soft threshold on the fly?  (fused 2D SWT kernels on every level)
 bool can_defer_soft(const pdwt_plan* p) {
@@ -1183,14 +1165,55 @@ bool can_defer_soft(const pdwt_plan* p) {
     return p->info.do_swt && p->info.ndims == 2 && p->do_separable && !no_lazy;
 }
 
-// soft / hard / proj_linf share one driver (pdwt/src/common.cu:219-308)
-int threshold_impl(pdwt_plan* p, int op, real_t beta, int do_app, int normalize, const char* what) {
-    if (p->state == PDWT_INVERSE)
-        return fail(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what);
-    {
-        const int rc = materialize_pending(p);
-        if (rc != PDWT_OK) return rc;
+// ---------------------------------------------------------------- the lazy state: one gate (lazy_state.hpp is the table)
+// does `e` turn a plan in this state down?  (the texts differ per entry point and stay with them)
+bool refuses(const pdwt_plan* p, Entry e) { return lazy_row(e).refuses_after_inverse && p->state == PDWT_INVERSE; }
+
+// What entry point `e` owes the coefficients before it touches them.  "apply": the deferred threshold runs now, as the sweep it
+// would have been.  "write back": one that the fused inverse applied on the fly never reached the stored details; it is applied to
+// them before they become observable again, so that no result depends on whether the fused path was taken.  Pending::consume is
+// pdwt_inverse's own; nothing else may read or write the two slots but the one place that defers (defer_soft).
+int settle_slow(pdwt_plan* p, LazyRow row) {
+    if (p->pending.on && row.pending != Pending::keep && row.pending != Pending::consume) {
+        p->pending.on = false;
+        if (row.pending == Pending::apply) {
+            const int rc = threshold_sweep(p, EW_SOFT, p->pending.beta, 0, p->pending.normalize, "soft_threshold");
+            if (rc != PDWT_OK) return rc;
+        }
     }
+    if (p->consumed.on && row.consumed != Consumed::keep) {
+        p->consumed.on = false;
+        if (row.consumed == Consumed::write_back)
+            return threshold_sweep(p, EW_SOFT, p->consumed.beta, 0, p->consumed.normalize, "soft_threshold");
+    }
+    return PDWT_OK;
+}
+
+inline int settle(pdwt_plan* p, Entry e) { return (p->pending.on | p->consumed.on) ? settle_slow(p, lazy_row(e)) : PDWT_OK; }
+
+// The preamble of an entry point, after its handle and argument checks: the plan's device becomes current and the row of `e` is
+// settled.  PDWT_ENTER_OR is for the rows that refuse after inverse(): `refusal` is what the call then returns.
+#define PDWT_SETTLE_(h, e)          \
+    DeviceGuard guard((h)->device); \
+    if (const int rc_ = settle((h), (e))) return rc_
+
+#define PDWT_ENTER(h, e)                                                                  \
+    static_assert(!lazy_row(e).refuses_after_inverse, "this row refuses: PDWT_ENTER_OR"); \
+    PDWT_SETTLE_(h, e)
+
+#define PDWT_ENTER_OR(h, e, refusal)                                                          \
+    static_assert(lazy_row(e).refuses_after_inverse, "this row does not refuse: PDWT_ENTER"); \
+    if (refuses((h), (e))) return (refusal);                                                  \
+    PDWT_SETTLE_(h, e)
+
+// the one place that makes a threshold pending (after the row of Entry::soft has been settled: an earlier one composes)
+bool defers(const pdwt_plan* p, real_t beta, int do_app) { return !do_app && beta >= real_t(0) && can_defer_soft(p); }
+void defer_soft(pdwt_plan* p, real_t beta, int normalize) { p->pending = {true, beta, normalize}; }
+
+// hard / proj_linf, and soft where it runs at once, share one driver (pdwt/src/common.cu:219-308)
+int threshold_impl(pdwt_plan* p, int op, real_t beta, int do_app, int normalize, const char* what) {
+    PDWT_ENTER_OR(p, Entry::eager_threshold,
+                  fail(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what));
     return threshold_sweep(p, op, beta, do_app, normalize, what);
 }
 
@@ -1350,6 +1373,44 @@ int threshold_bands_impl(pdwt_plan* p, int op, const real_t* d_table) {
     return PDWT_OK;
 }
 
+// the two sums over the coefficient region, into `d_out2` or the plan's own slot; nothing is synchronised
+int norms_into(pdwt_plan* p, double* d_out2) {
+    Stamp st(p, "norms");
+    HIP_TRY(launch_norms(p->arena, p->coeff_elems, p->d_red, d_out2 ? d_out2 : p->d_red, p->stream));
+    return PDWT_OK;
+}
+
+// `n` values to host memory: the body of the host getters, which return the count
+long long copy_out(pdwt_plan* p, real_t* dst, const real_t* src, long long n) {
+    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)n * sizeof(real_t), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return n;
+}
+
+// `n` values from host or device memory into the plan.  The plan's own buffer as the source (the caller filled it through
+// pdwt_image_ptr / pdwt_coeff_ptr, on the plan's stream or ordered with it by pdwt_wait_for_stream): nothing to copy, nothing to
+// wait for.  Otherwise the copy has completed when the call returns, host AND device sources, so the caller may reuse or free the
+// source at once (a torch temporary goes back to the caching allocator as soon as the Python call returns).  Ordering of the
+// source's PRODUCER with this copy is the caller's: pdwt_wait_for_stream / pdwt_sync_producer.
+int copy_in(pdwt_plan* p, real_t* dst, const real_t* src, long long n, int mem_is_on_device) {
+    if (mem_is_on_device && src == dst) return PDWT_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)n * sizeof(real_t), mem_is_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                           p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return PDWT_OK;
+}
+
+// four len x len banks of a non-separable plan, to banks `first` .. `first` + 3 (forward: 0, inverse: 4)
+int upload_f2d(pdwt_plan* p, int first, unsigned len, const real_t* const f[4]) {
+    if (!p->d_f2d) HIP_TRY(device_malloc((void**)&p->d_f2d, (size_t)8 * kMaxTaps * kMaxTaps * sizeof(real_t)));
+    for (int k = 0; k < 4; k++)
+        HIP_TRY(hipMemcpyAsync(p->d_f2d + (size_t)(first + k) * len * len, f[k], (size_t)len * len * sizeof(real_t),
+                               hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->f2d_custom = true;
+    return PDWT_OK;
+}
+
 std::string info_text(pdwt_plan* p) {
     // same lines as Wavelets::print_informations (pdwt/src/wt.cu:511-550)
     char buf[1024];
@@ -1403,14 +1464,7 @@ int pdwt_clone(pdwt_handle src, pdwt_handle* out) {
     CHECK_HANDLE(src);
     if (!out) return fail(PDWT_ERR_ARG, "pdwt_clone: out is null");
     *out = nullptr;
-    DeviceGuard guard(src->device);
-    {
-        // the copy must not depend on whether the source took the fused path: a deferred threshold is applied and one
-        // that the fused inverse consumed on the fly is written back before the arena is copied
-        int rc0 = materialize_pending(src);
-        if (rc0 == PDWT_OK) rc0 = materialize_consumed(src);
-        if (rc0 != PDWT_OK) return rc0;
-    }
+    PDWT_ENTER(src, Entry::clone);  // the copy must not depend on whether the source took the fused path
     pdwt_plan* p = new pdwt_plan();
     p->device = src->device;
     p->batch = src->batch;
@@ -1472,9 +1526,7 @@ int pdwt_forward(pdwt_handle h) {  // Wavelets::forward, wt.cu:236-269
     CHECK_HANDLE(h);
     if (h->state == PDWT_CREATION_ERROR)
         return fail(PDWT_ERR_STATE, "forward transform not computed, as there was an error when creating the wavelets");
-    DeviceGuard guard(h->device);
-    h->pend_soft = false;  // the coefficients a deferred threshold referred to are about to be overwritten
-    h->soft_consumed = false;
+    PDWT_ENTER(h, Entry::forward);
     if (h->do_cycle_spinning) {  // wt.cu:242-246
         h->shift_r = rand() % h->info.Nr;
         h->shift_c = rand() % h->info.Nc;
@@ -1488,18 +1540,12 @@ int pdwt_forward(pdwt_handle h) {  // Wavelets::forward, wt.cu:236-269
 
 int pdwt_inverse(pdwt_handle h) {  // Wavelets::inverse, wt.cu:271-305
     CHECK_HANDLE(h);
-    if (h->state == PDWT_INVERSE)
-        return fail(PDWT_ERR_STATE, "W.inverse() has already been run. Inverse is available in W.get_image()");
+    PDWT_ENTER_OR(h, Entry::inverse, fail(PDWT_ERR_STATE, "W.inverse() has already been run. Inverse is available in W.get_image()"));
     if (h->state == PDWT_FORWARD_ERROR || h->state == PDWT_THRESHOLD_ERROR || h->state == PDWT_CREATION_ERROR)
         return fail(PDWT_ERR_STATE, "inverse transform not computed, as there was an error in a previous stage");
-    DeviceGuard guard(h->device);
     int rc = inverse_impl(h);
-    if (h->pend_soft && rc == PDWT_OK) {  // consumed by the fused kernels, not written back (materialize_consumed)
-        h->soft_consumed = true;
-        h->consumed_beta = h->pend_beta;
-        h->consumed_normalize = h->pend_normalize;
-    }
-    h->pend_soft = false;
+    if (h->pending.on && rc == PDWT_OK) h->consumed = h->pending;  // Pending::consume: applied by the fused kernels, not written back
+    h->pending.on = false;
     if (rc == PDWT_OK && h->do_cycle_spinning) rc = circshift_impl(h, -h->shift_r, -h->shift_c, 1);  // wt.cu:303
     h->state = (rc == PDWT_OK) ? PDWT_INVERSE : PDWT_INVERSE_ERROR;
     return rc;
@@ -1507,39 +1553,25 @@ int pdwt_inverse(pdwt_handle h) {  // Wavelets::inverse, wt.cu:271-305
 
 int pdwt_soft_threshold(pdwt_handle h, real_t beta, int do_app, int normalize) {  // wt.cu:308-315
     CHECK_HANDLE(h);
-    DeviceGuard guard(h->device);
-    if (h->state != PDWT_INVERSE && !do_app && beta >= 0.f && can_defer_soft(h)) {
-        const int rc = materialize_pending(h);  // an earlier pending threshold composes: apply it first
-        if (rc != PDWT_OK) return rc;
-        h->pend_soft = true;
-        h->pend_beta = beta;
-        h->pend_normalize = normalize;
-        return PDWT_OK;
-    }
-    return threshold_impl(h, EW_SOFT, beta, do_app, normalize, "soft_threshold");
+    PDWT_ENTER_OR(h, Entry::soft, fail(PDWT_ERR_STATE, "soft_threshold: cannot threshold coefficients, as they were modified by inverse()"));
+    if (!defers(h, beta, do_app)) return threshold_sweep(h, EW_SOFT, beta, do_app, normalize, "soft_threshold");
+    defer_soft(h, beta, normalize);
+    return PDWT_OK;
 }
 
 int pdwt_hard_threshold(pdwt_handle h, real_t beta, int do_app, int normalize) {  // wt.cu:318-325
     CHECK_HANDLE(h);
-    DeviceGuard guard(h->device);
     return threshold_impl(h, EW_HARD, beta, do_app, normalize, "hard_threshold");
 }
 
 int pdwt_proj_linf(pdwt_handle h, real_t beta, int do_app) {  // wt.cu:349-356
     CHECK_HANDLE(h);
-    DeviceGuard guard(h->device);
     return threshold_impl(h, EW_LINF, beta, do_app, 0, "proj_linf");
 }
 
 int pdwt_group_soft_threshold(pdwt_handle h, real_t beta, int do_app, int normalize) {  // wt.cu:329-336
     CHECK_HANDLE(h);
-    if (h->state == PDWT_INVERSE)
-        return fail(PDWT_ERR_STATE, "cannot threshold coefficients, as they were modified by inverse()");
-    DeviceGuard guard(h->device);
-    {
-        const int rc0 = materialize_pending(h);
-        if (rc0 != PDWT_OK) return rc0;
-    }
+    PDWT_ENTER_OR(h, Entry::eager_threshold, fail(PDWT_ERR_STATE, "cannot threshold coefficients, as they were modified by inverse()"));
     const int L = h->info.nlevels, B = h->batch;
     const int per = h->info.ndims == 2 ? 3 : 1;
     for (int l = 1; l <= L; l++) {  // common.cu:311-341
@@ -1556,13 +1588,7 @@ int pdwt_group_soft_threshold(pdwt_handle h, real_t beta, int do_app, int normal
 
 int pdwt_shrink(pdwt_handle h, real_t beta, int do_app) {  // wt.cu:340-347, common.cu:347-371
     CHECK_HANDLE(h);
-    if (h->state == PDWT_INVERSE)
-        return fail(PDWT_ERR_STATE, "cannot threshold coefficients, as they were modified by inverse()");
-    DeviceGuard guard(h->device);
-    {
-        const int rc0 = materialize_pending(h);
-        if (rc0 != PDWT_OK) return rc0;
-    }
+    PDWT_ENTER_OR(h, Entry::eager_threshold, fail(PDWT_ERR_STATE, "cannot threshold coefficients, as they were modified by inverse()"));
     const long long first = do_app ? 0 : h->bands[1].off;
     Stamp st(h, "shrink");
     HIP_TRY(launch_ew(EW_SCALE, h->arena + first, h->coeff_elems - first, 1.0f / (1.0f + beta), h->stream));
@@ -1571,23 +1597,15 @@ int pdwt_shrink(pdwt_handle h, real_t beta, int do_app) {  // wt.cu:340-347, com
 
 int pdwt_circshift(pdwt_handle h, int sr, int sc, int inplace) {
     CHECK_HANDLE(h);
-    DeviceGuard guard(h->device);
+    PDWT_ENTER(h, Entry::untouched);
     return circshift_impl(h, sr, sc, inplace);
 }
 
 static int norms_impl(pdwt_handle h, double out[2]) {
-    DeviceGuard guard(h->device);
-    {
-        // the sums are over what a reader of the coefficients would see: a deferred threshold is applied, and one that the fused
-        // inverse consumed on the fly is written back (norm1() after soft_threshold(); inverse() is the objective of an ISTA step)
-        int rc0 = materialize_pending(h);
-        if (rc0 == PDWT_OK) rc0 = materialize_consumed(h);
-        if (rc0 != PDWT_OK) return rc0;
-    }
-    {
-        Stamp st(h, "norms");
-        HIP_TRY(launch_norms(h->arena, h->coeff_elems, h->d_red, h->d_red, h->stream));
-    }
+    // the sums are over what a reader of the coefficients would see (norm1() after soft_threshold(); inverse() is the objective of
+    // an ISTA step)
+    PDWT_ENTER(h, Entry::norms);
+    if (const int rc = norms_into(h, nullptr)) return rc;
     if (!h->h_red && hipHostMalloc((void**)&h->h_red, 2 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
         h->h_red = nullptr;
@@ -1604,13 +1622,8 @@ static int norms_impl(pdwt_handle h, double out[2]) {
 // wants to.  The blocking getters below stay for API parity (wt.cu:368-416 return host floats).
 int pdwt_norms_async(pdwt_handle h, double* d_out2) {
     CHECK_HANDLE(h);
-    DeviceGuard guard(h->device);
-    int rc0 = materialize_pending(h);
-    if (rc0 == PDWT_OK) rc0 = materialize_consumed(h);  // see norms_impl
-    if (rc0 != PDWT_OK) return rc0;
-    Stamp st(h, "norms");
-    HIP_TRY(launch_norms(h->arena, h->coeff_elems, h->d_red, d_out2 ? d_out2 : h->d_red, h->stream));
-    return PDWT_OK;
+    PDWT_ENTER(h, Entry::norms);
+    return norms_into(h, d_out2);
 }
 
 int pdwt_norms_slot(pdwt_handle h, double** d_ptr) {
@@ -1625,26 +1638,15 @@ int pdwt_norms_slot(pdwt_handle h, double** d_ptr) {
 // whose inverse applies the threshold as it loads the details (2D SWT) keeps doing so: the sweep is then read-only.
 int pdwt_soft_threshold_norms_async(pdwt_handle h, real_t beta, int do_app, int normalize, double* d_out2) {
     CHECK_HANDLE(h);
-    DeviceGuard guard(h->device);
-    if (h->state == PDWT_INVERSE)
-        return fail(PDWT_ERR_STATE, "soft_threshold: cannot threshold coefficients, as they were modified by inverse()");
-    const int rc0 = materialize_pending(h);  // an earlier pending threshold composes: apply it first
-    if (rc0 != PDWT_OK) return rc0;
+    PDWT_ENTER_OR(h, Entry::soft, fail(PDWT_ERR_STATE, "soft_threshold: cannot threshold coefficients, as they were modified by inverse()"));
     if (beta < real_t(0)) {
         // soft(0, beta) = |beta|: the one-sweep form would count the padding in and leave it dirty (see rezero_padding); this rare
         // case runs as the threshold and then the norms
         const int rc = threshold_sweep(h, EW_SOFT, beta, do_app, normalize, "soft_threshold");
-        if (rc != PDWT_OK) return rc;
-        Stamp st(h, "norms");
-        HIP_TRY(launch_norms(h->arena, h->coeff_elems, h->d_red, d_out2 ? d_out2 : h->d_red, h->stream));
-        return PDWT_OK;
+        return rc != PDWT_OK ? rc : norms_into(h, d_out2);
     }
-    const bool defer = !do_app && beta >= 0.f && can_defer_soft(h);
-    if (defer) {
-        h->pend_soft = true;
-        h->pend_beta = beta;
-        h->pend_normalize = normalize;
-    }
+    const bool defer = defers(h, beta, do_app);
+    if (defer) defer_soft(h, beta, normalize);
     const int L = h->info.nlevels, per = h->info.ndims == 2 ? 3 : 1;
     const long long first = h->bands[1].off;
     double* out = d_out2 ? d_out2 : h->d_red;
@@ -1674,26 +1676,20 @@ int pdwt_soft_threshold_norms_async(pdwt_handle h, real_t beta, int do_app, int 
 }
 
 // ---------------------------------------------------------------- NEW: adaptive denoising (no reference counterpart)
-// The two read-only operators take what pdwt_norms_async takes: a deferred threshold is applied, one that the fused inverse
-// consumed on the fly is written back, and the sums / the median are those of what a reader of the coefficients would see.
+// The two read-only operators take what pdwt_norms_async takes: the sums / the median are those of what a reader of the
+// coefficients would see.
 int pdwt_band_stats_async(pdwt_handle h, double* d_out) {
     CHECK_HANDLE(h);
-    DeviceGuard guard(h->device);
-    int rc = materialize_pending(h);
-    if (rc == PDWT_OK) rc = materialize_consumed(h);
-    if (rc == PDWT_OK) rc = ensure_adaptive(h);
-    if (rc != PDWT_OK) return rc;
-    return band_stats_impl(h, d_out);
+    PDWT_ENTER(h, Entry::read_stats);
+    const int rc = ensure_adaptive(h);
+    return rc != PDWT_OK ? rc : band_stats_impl(h, d_out);
 }
 
 int pdwt_estimate_sigma_async(pdwt_handle h, int skip_zeros, double* d_out) {
     CHECK_HANDLE(h);
-    DeviceGuard guard(h->device);
-    int rc = materialize_pending(h);
-    if (rc == PDWT_OK) rc = materialize_consumed(h);
-    if (rc == PDWT_OK) rc = ensure_adaptive(h);
-    if (rc != PDWT_OK) return rc;
-    return estimate_sigma_impl(h, skip_zeros, d_out);
+    PDWT_ENTER(h, Entry::read_stats);
+    const int rc = ensure_adaptive(h);
+    return rc != PDWT_OK ? rc : estimate_sigma_impl(h, skip_zeros, d_out);
 }
 
 // The two sweeps follow pdwt_soft_threshold (wt.cu:308-315): refused after inverse(), a deferred threshold composes (it is
@@ -1703,11 +1699,9 @@ int pdwt_threshold_bands(pdwt_handle h, int op, const real_t* table, int table_o
     CHECK_HANDLE(h);
     if (!table) return fail(PDWT_ERR_ARG, "threshold_bands: null table");
     if (op != EW_SOFT && op != EW_HARD) return fail(PDWT_ERR_ARG, "threshold_bands: op must be 0 (soft) or 1 (hard)");
-    if (h->state == PDWT_INVERSE)
-        return fail(PDWT_ERR_STATE, "threshold_bands: cannot threshold coefficients, as they were modified by inverse()");
-    DeviceGuard guard(h->device);
-    int rc = materialize_pending(h);
-    if (rc == PDWT_OK) rc = ensure_adaptive(h);
+    PDWT_ENTER_OR(h, Entry::band_sweep,
+                  fail(PDWT_ERR_STATE, "threshold_bands: cannot threshold coefficients, as they were modified by inverse()"));
+    int rc = ensure_adaptive(h);
     if (rc != PDWT_OK) return rc;
     AdaptiveWs* w = h->adaptive;
     if (!table_on_device) {
@@ -1724,11 +1718,8 @@ int pdwt_denoise_async(pdwt_handle h, int method, int op, const double* sigma, i
     if (op != EW_SOFT && op != EW_HARD) return fail(PDWT_ERR_ARG, "denoise: op must be 0 (soft) or 1 (hard)");
     if (sigma && nsigma != 1 && nsigma != h->batch)
         return fail(PDWT_ERR_ARG, "denoise: %d noise levels for %d images (one, or one per image)", nsigma, h->batch);
-    if (h->state == PDWT_INVERSE)
-        return fail(PDWT_ERR_STATE, "denoise: cannot threshold coefficients, as they were modified by inverse()");
-    DeviceGuard guard(h->device);
-    int rc = materialize_pending(h);
-    if (rc == PDWT_OK) rc = ensure_adaptive(h);
+    PDWT_ENTER_OR(h, Entry::band_sweep, fail(PDWT_ERR_STATE, "denoise: cannot threshold coefficients, as they were modified by inverse()"));
+    int rc = ensure_adaptive(h);
     if (rc != PDWT_OK) return rc;
     AdaptiveWs* w = h->adaptive;
     if (sigma) {
@@ -1784,7 +1775,7 @@ int pdwt_add_wavelet(pdwt_handle dst, pdwt_handle src, real_t alpha) {  // wt.cu
         fail(PDWT_ERR_MISMATCH, "add_wavelet(): right operand is not the same transform (wname, level)");
         return -1;
     }
-    if (dst->state == PDWT_INVERSE || src->state == PDWT_INVERSE) {
+    if (refuses(dst, Entry::add_wavelet) || refuses(src, Entry::add_wavelet)) {
         fail(PDWT_ERR_STATE, "add_wavelet(): this operation makes no sense when wavelet has just been inverted");
         return 1;
     }
@@ -1807,11 +1798,8 @@ int pdwt_add_wavelet(pdwt_handle dst, pdwt_handle src, real_t alpha) {  // wt.cu
         return -2;
     }
     DeviceGuard guard(dst->device);
-    {
-        int rc0 = materialize_pending(dst);
-        if (rc0 == PDWT_OK) rc0 = materialize_pending(src);
-        if (rc0 != PDWT_OK) return rc0;
-    }
+    if (const int rc = settle(dst, Entry::add_wavelet)) return rc;
+    if (const int rc = settle(src, Entry::add_wavelet)) return rc;
     if (src->stream != dst->stream) HIP_TRY(hipStreamSynchronize(src->stream));
     Stamp st(dst, "add_wavelet");
     HIP_TRY(launch_axpy(dst->arena, src->arena, dst->coeff_elems, alpha, dst->stream));
@@ -1820,11 +1808,8 @@ int pdwt_add_wavelet(pdwt_handle dst, pdwt_handle src, real_t alpha) {  // wt.cu
 
 long long pdwt_get_image(pdwt_handle h, real_t* dst) {  // wt.cu:419-422
     if (!h || !dst) return fail(PDWT_ERR_ARG, "pdwt_get_image: null argument");
-    DeviceGuard guard(h->device);
-    const long long n = (long long)h->batch * h->info.Nr * h->info.Nc;
-    HIP_TRY(hipMemcpyAsync(dst, h->image(), (size_t)n * sizeof(real_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return n;
+    PDWT_ENTER(h, Entry::untouched);
+    return copy_out(h, dst, h->image(), (long long)h->batch * h->info.Nr * h->info.Nc);
 }
 
 long long pdwt_coeff_count(pdwt_handle h, int num, int* rows, int* cols) {
@@ -1835,22 +1820,15 @@ long long pdwt_coeff_count(pdwt_handle h, int num, int* rows, int* cols) {
     return h->bands[num].elems(h->batch);
 }
 
+// what the three coefficient getters answer after inverse(): 0 values, not an error code (wt.cu:473-477)
+#define GET_COEFF_REFUSAL \
+    (fail(PDWT_ERR_STATE, "get_coeff(): inverse() has been performed, the coefficients has been modified and do not make sense anymore."), 0)
+
 long long pdwt_get_coeff(pdwt_handle h, real_t* dst, int num) {  // wt.cu:473-506
     if (!h || !dst) return fail(PDWT_ERR_ARG, "pdwt_get_coeff: null argument");
     if (num < 0 || num >= (int)h->bands.size()) return fail(PDWT_ERR_ARG, "coefficient index %d out of range", num);
-    if (h->state == PDWT_INVERSE) {
-        fail(PDWT_ERR_STATE, "get_coeff(): inverse() has been performed, the coefficients has been modified and do not make sense anymore.");
-        return 0;
-    }
-    DeviceGuard guard(h->device);
-    {
-        const int rc0 = materialize_pending(h);
-        if (rc0 != PDWT_OK) return rc0;
-    }
-    const long long n = h->bands[num].elems(h->batch);
-    HIP_TRY(hipMemcpyAsync(dst, h->band(num), (size_t)n * sizeof(real_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return n;
+    PDWT_ENTER_OR(h, Entry::get_coeff, GET_COEFF_REFUSAL);
+    return copy_out(h, dst, h->band(num), h->bands[num].elems(h->batch));
 }
 
 long long pdwt_coeff_region(pdwt_handle h, long long* band_offsets, int capacity) {
@@ -1862,31 +1840,17 @@ long long pdwt_coeff_region(pdwt_handle h, long long* band_offsets, int capacity
 
 long long pdwt_get_coeff_region(pdwt_handle h, real_t* dst) {
     if (!h || !dst) return fail(PDWT_ERR_ARG, "pdwt_get_coeff_region: null argument");
-    if (h->state == PDWT_INVERSE) {
-        fail(PDWT_ERR_STATE, "get_coeff(): inverse() has been performed, the coefficients has been modified and do not make sense anymore.");
-        return 0;
-    }
-    DeviceGuard guard(h->device);
-    {
-        const int rc0 = materialize_pending(h);
-        if (rc0 != PDWT_OK) return rc0;
-    }
-    const long long n = h->coeff_elems - h->bands[0].off;
-    HIP_TRY(hipMemcpyAsync(dst, h->band(0), (size_t)n * sizeof(real_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return n;
+    PDWT_ENTER_OR(h, Entry::get_coeff, GET_COEFF_REFUSAL);
+    return copy_out(h, dst, h->band(0), h->coeff_elems - h->bands[0].off);
 }
 
 long long pdwt_get_image_at(pdwt_handle h, real_t* dst, int image_index) {  // wt.cu:419-422, one image of a batch
     if (!h || !dst) return fail(PDWT_ERR_ARG, "pdwt_get_image_at: null argument");
     if (image_index < 0 || image_index >= h->batch)
         return fail(PDWT_ERR_ARG, "pdwt_get_image_at: image %d out of range (batch %d)", image_index, h->batch);
-    DeviceGuard guard(h->device);
+    PDWT_ENTER(h, Entry::untouched);
     const long long n = (long long)h->info.Nr * h->info.Nc;
-    HIP_TRY(hipMemcpyAsync(dst, h->image() + (long long)image_index * n, (size_t)n * sizeof(real_t),
-                           hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return n;
+    return copy_out(h, dst, h->image() + (long long)image_index * n, n);
 }
 
 long long pdwt_get_coeff_at(pdwt_handle h, real_t* dst, int num, int image_index) {  // wt.cu:473-506, one image
@@ -1894,44 +1858,19 @@ long long pdwt_get_coeff_at(pdwt_handle h, real_t* dst, int num, int image_index
     if (num < 0 || num >= (int)h->bands.size()) return fail(PDWT_ERR_ARG, "coefficient index %d out of range", num);
     if (image_index < 0 || image_index >= h->batch)
         return fail(PDWT_ERR_ARG, "pdwt_get_coeff_at: image %d out of range (batch %d)", image_index, h->batch);
-    if (h->state == PDWT_INVERSE) {
-        fail(PDWT_ERR_STATE, "get_coeff(): inverse() has been performed, the coefficients has been modified and do not make sense anymore.");
-        return 0;
-    }
-    DeviceGuard guard(h->device);
-    {
-        const int rc0 = materialize_pending(h);
-        if (rc0 != PDWT_OK) return rc0;
-    }
+    PDWT_ENTER_OR(h, Entry::get_coeff, GET_COEFF_REFUSAL);
     const long long n = h->bands[num].elems(1);
-    HIP_TRY(hipMemcpyAsync(dst, h->band(num) + (long long)image_index * n, (size_t)n * sizeof(real_t),
-                           hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return n;
+    return copy_out(h, dst, h->band(num) + (long long)image_index * n, n);
 }
 
 int pdwt_set_image(pdwt_handle h, const real_t* src, int mem_is_on_device) {  // wt.cu:425-431
     CHECK_HANDLE(h);
     if (!src) return fail(PDWT_ERR_ARG, "pdwt_set_image: src is null");
-    DeviceGuard guard(h->device);
-    const long long n = (long long)h->batch * h->info.Nr * h->info.Nc;
-    // the plan's own image buffer (the caller filled it through pdwt_image_ptr, on the plan's stream or ordered with it
-    // by pdwt_wait_for_stream): nothing to copy, nothing to wait for -- the call only makes the image current
-    const bool in_place = mem_is_on_device && src == h->image();
-    if (!in_place) {
-        HIP_TRY(hipMemcpyAsync(h->image(), src, (size_t)n * sizeof(real_t),
-                               mem_is_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    // host AND device sources: the copy has completed when the call returns, so the caller may reuse or free the
-    // source at once (a torch temporary goes back to the caching allocator as soon as the Python call returns).
-    // Ordering of the source's PRODUCER with this copy is the caller's: pdwt_wait_for_stream / pdwt_sync_producer.
     // a threshold the fused inverse applied on the fly is written back before the state leaves PDWT_INVERSE:
     // get_coeff / norms / add_wavelet are legal again after set_image and must see thresholded details (wt.cu:308-315)
-    {
-        const int rc0 = materialize_consumed(h);
-        if (rc0 != PDWT_OK) return rc0;
-    }
+    PDWT_ENTER(h, Entry::set_image);
+    const int rc = copy_in(h, h->image(), src, (long long)h->batch * h->info.Nr * h->info.Nc, mem_is_on_device);
+    if (rc != PDWT_OK) return rc;
     h->state = PDWT_INIT;
     return PDWT_OK;
 }
@@ -1940,18 +1879,9 @@ int pdwt_set_coeff(pdwt_handle h, const real_t* src, int num, int mem_is_on_devi
     CHECK_HANDLE(h);
     if (!src) return fail(PDWT_ERR_ARG, "pdwt_set_coeff: src is null");
     if (num < 0 || num >= (int)h->bands.size()) return fail(PDWT_ERR_ARG, "coefficient index %d out of range", num);
-    DeviceGuard guard(h->device);
-    {
-        int rc0 = materialize_pending(h);  // a deferred threshold applies to the OLD contents only
-        if (rc0 == PDWT_OK) rc0 = materialize_consumed(h);
-        if (rc0 != PDWT_OK) return rc0;
-    }
-    const long long n = h->bands[num].elems(h->batch);
-    if (!(mem_is_on_device && src == h->band(num))) {  // the band's own buffer: in place, see pdwt_set_image
-        HIP_TRY(hipMemcpyAsync(h->band(num), src, (size_t)n * sizeof(real_t),
-                               mem_is_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));  // see pdwt_set_image
-    }
+    PDWT_ENTER(h, Entry::set_coeff);  // a deferred threshold applies to the OLD contents only
+    const int rc = copy_in(h, h->band(num), src, h->bands[num].elems(h->batch), mem_is_on_device);
+    if (rc != PDWT_OK) return rc;
     // The reference forbids coefficient access after inverse() because its inverse overwrites the
     // approximation band d_coeffs[0] (wt.cu:272-275); once the caller has supplied that band again the
     // coefficients are current, so a new inverse() is meaningful (the reference would still refuse it).
@@ -1985,11 +1915,8 @@ int pdwt_copy(pdwt_handle h, void* dst, const void* src, long long count, int ki
 
 intptr_t pdwt_coeff_ptr(pdwt_handle h, int num) {
     if (!h || num < 0 || num >= (int)h->bands.size()) return 0;
-    {
-        DeviceGuard guard(h->device);
-        // the caller will read device memory directly
-        if (materialize_pending(h) != PDWT_OK || materialize_consumed(h) != PDWT_OK) return 0;
-    }
+    DeviceGuard guard(h->device);
+    if (settle(h, Entry::coeff_ptr) != PDWT_OK) return 0;  // the caller will read device memory directly
     return (intptr_t)h->band(num);
 }
 
@@ -2000,7 +1927,7 @@ int pdwt_set_filters_forward(pdwt_handle h, const char* name, unsigned int len, 
         return fail(PDWT_ERR_FILTER_LEN, "set_filters_forward(): filter length (%u) exceeds the maximum size (%d)", len,
                     PDWT_MAX_FILTER_WIDTH);
     if (!f1 || !f2) return fail(PDWT_ERR_ARG, "set_filters_forward(): filter1/filter2 are required");
-    DeviceGuard guard(h->device);
+    PDWT_ENTER(h, Entry::untouched);
     if (h->do_separable) {
         memset(&h->dec, 0, sizeof(h->dec));
         memcpy(h->dec.lo, f1, len * sizeof(real_t));
@@ -2008,13 +1935,8 @@ int pdwt_set_filters_forward(pdwt_handle h, const char* name, unsigned int len, 
     } else {
         if (!f3 || !f4)
             return fail(PDWT_ERR_ARG, "set_filters_forward(): expected argument 4 and 5 for non-separable filtering");
-        if (!h->d_f2d) HIP_TRY(device_malloc((void**)&h->d_f2d, (size_t)8 * kMaxTaps * kMaxTaps * sizeof(real_t)));
         const real_t* f[4] = {f1, f2, f3, f4};
-        for (int k = 0; k < 4; k++)
-            HIP_TRY(hipMemcpyAsync(h->d_f2d + (size_t)k * len * len, f[k], (size_t)len * len * sizeof(real_t),
-                                   hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->f2d_custom = true;
+        if (const int rc = upload_f2d(h, 0, len, f)) return rc;
     }
     h->info.hlen = (int)len;
     if (name) snprintf(h->wname, sizeof(h->wname), "%s", name);
@@ -2027,7 +1949,7 @@ int pdwt_set_filters_inverse(pdwt_handle h, const real_t* f1, const real_t* f2, 
     CHECK_HANDLE(h);
     if (!f1 || !f2) return fail(PDWT_ERR_ARG, "set_filters_inverse(): filter1/filter2 are required");
     const unsigned len = (unsigned)h->info.hlen;
-    DeviceGuard guard(h->device);
+    PDWT_ENTER(h, Entry::untouched);
     if (h->do_separable) {
         memset(&h->rec, 0, sizeof(h->rec));
         memcpy(h->rec.lo, f1, len * sizeof(real_t));
@@ -2035,13 +1957,8 @@ int pdwt_set_filters_inverse(pdwt_handle h, const real_t* f1, const real_t* f2, 
     } else {
         if (!f3 || !f4)
             return fail(PDWT_ERR_ARG, "set_filters_inverse(): expected argument 4 and 5 for non-separable filtering");
-        if (!h->d_f2d) HIP_TRY(device_malloc((void**)&h->d_f2d, (size_t)8 * kMaxTaps * kMaxTaps * sizeof(real_t)));
         const real_t* f[4] = {f1, f2, f3, f4};
-        for (int k = 0; k < 4; k++)
-            HIP_TRY(hipMemcpyAsync(h->d_f2d + (size_t)(4 + k) * len * len, f[k], (size_t)len * len * sizeof(real_t),
-                                   hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->f2d_custom = true;
+        if (const int rc = upload_f2d(h, 4, len, f)) return rc;
     }
     return PDWT_OK;
 }

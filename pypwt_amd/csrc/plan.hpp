@@ -25,6 +25,7 @@
 #include "../../include/pypwt_amd_bench.h"
 #include "kernels_common.hpp"
 #include "launch.hpp"
+#include "lazy_state.hpp"
 
 namespace pdwt {
 
@@ -66,6 +67,13 @@ struct AdaptiveWs {
     hipEvent_t staged = nullptr;
 };
 
+// a soft threshold of the detail bands that a plan owes its coefficients (pdwt_plan::pending, ::consumed)
+struct LazyThreshold {
+    bool on = false;
+    real_t beta = 0.f;
+    int normalize = 0;
+};
+
 }  // namespace pdwt
 
 struct pdwt_plan {
@@ -100,17 +108,11 @@ struct pdwt_plan {
     real_t* d_f2d = nullptr;  // non-separable banks: fwd LL,LH,HL,HH then inv, each hlen*hlen
     bool f2d_custom = false;
 
-    // A soft_threshold that has been requested but not yet applied: the fused SWT inverse applies
-    // it while it loads the detail bands (saves one read+write sweep of 3L full-size planes); any
-    // other consumer of the coefficients materialises it first (plan.cpp: materialize_pending).
-    bool pend_soft = false;
-    real_t pend_beta = 0.f;
-    int pend_normalize = 0;
-    // ... and one that the fused inverse has applied on the fly without writing the thresholded details
-    // back (plan.cpp: materialize_consumed)
-    bool soft_consumed = false;
-    real_t consumed_beta = 0.f;
-    int consumed_normalize = 0;
+    // The lazy state (lazy_state.hpp).  pending: a soft_threshold that has been requested but not yet applied -- the fused SWT
+    // inverse applies it while it loads the detail bands (saves one read+write sweep of 3L full-size planes).  consumed: one that
+    // such an inverse has applied on the fly without writing the thresholded details back.  Every entry point settles what its
+    // row of the table owes them before it touches the coefficients (plan.cpp: settle).
+    pdwt::LazyThreshold pending, consumed;
 
     std::vector<pdwt::Step> sched_fwd, sched_inv;  // launch lists, in execution order
     pdwt::Tuning tune{};  // the dispatch knobs as they stood when the plan was created (launch.hpp: ActiveTuning)

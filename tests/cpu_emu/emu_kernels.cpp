@@ -33,6 +33,7 @@
 #include "../../pypwt_amd/csrc/swt_stream_kernels.hpp"
 #include "../../pypwt_amd/csrc/dwt2_stream_kernels.hpp"
 #include "../../pypwt_amd/csrc/dwt2_split_kernels.hpp"
+#include "../../pypwt_amd/csrc/lazy_state.hpp"
 
 using namespace pdwt;
 
@@ -1432,4 +1433,15 @@ EMU_API int emu_dwt2_inv_long(const float* A, const float* H, const float* V, co
 #undef X
     }
     return -1;
+}
+
+// one row of the lazy-state table (lazy_state.hpp): {refuses after inverse(), what becomes of a pending threshold, of a consumed one};
+// -1 past the last Entry
+EMU_API int emu_lazy_row(int entry, int* out3) {
+    if (entry < 0 || entry >= (int)pdwt::Entry::count_) return -1;
+    const pdwt::LazyRow r = pdwt::lazy_row((pdwt::Entry)entry);
+    out3[0] = r.refuses_after_inverse;
+    out3[1] = (int)r.pending;
+    out3[2] = (int)r.consumed;
+    return 0;
 }

@@ -1,7 +1,7 @@
 """An EAGER host model of one plan of include/pypwt_amd.h, and the generator of the call sequences it judges.
 
-The library keeps two pieces of lazy state beside the reference's `state` enum (plan.cpp: `pend_soft`, a soft threshold that the
-fused 2D SWT inverse applies while it loads the details, and `soft_consumed`, the write-back such an inverse still owes).  The
+The library keeps two pieces of lazy state beside the reference's `state` enum (plan.hpp: `pending`, a soft threshold that the
+fused 2D SWT inverse applies while it loads the details, and `consumed`, the write-back such an inverse still owes).  The
 model has neither: every operator is applied to its bands at once, so whatever the library returns after ANY order of calls has
 one right answer here.  tests/test_gpu_sequences.py drives both with the same calls; tests/test_plan_model_cpu.py pins the model
 to the CPU oracle and checks the conditions on the generated sequences without a GPU.
@@ -458,7 +458,8 @@ def refused(op, rc):
 
 # --------------------------------------------------------------------------------------------------------------- the generator
 class Situation(object):
-    """The lazy state of plan.cpp restated: what a deferring plan (can_defer_soft: separable 2D SWT) would hold after each call.
+    """The table of lazy_state.hpp (what plan.cpp's settle() performs) restated: what a deferring plan (can_defer_soft: separable
+    2D SWT) would hold after each call.
     Tracked for every plan, deferring or not, so that all of them get the same kind of sequences."""
 
     def __init__(self):
@@ -485,15 +486,15 @@ class Situation(object):
             self.state, self.consumed, self.pending = INVERSE, self.pending, False
         elif k in ("soft", "soft_norms"):
             beta, do_app = op[1], op[2]
-            self.pending = (not do_app) and beta >= 0   # pdwt_soft_threshold: `!do_app && beta >= 0 && can_defer_soft(h)`
+            self.pending = (not do_app) and beta >= 0   # plan.cpp, defers(): `!do_app && beta >= 0 && can_defer_soft(p)`
         elif k in ("hard", "group", "shrink", "linf", "get_coeff", "get_coeff_at", "get_region", "add_dst", "add_src"):
-            self.pending = False                         # materialize_pending
+            self.pending = False                         # Pending::apply
         elif k in ("norm1", "norm2sq", "norms_async"):
             self.pending = self.consumed = False         # the sums are over what a reader would see
         elif k in ("raw_read", "clone"):
-            self.pending = self.consumed = False         # materialize_pending + materialize_consumed
+            self.pending = self.consumed = False         # Pending::apply + Consumed::write_back
         elif k == "set_image":
-            self.consumed = False                        # materialize_consumed; a pending threshold stays pending
+            self.consumed = False                        # Consumed::write_back; a pending threshold stays pending
             self.state = INIT
         elif k == "set_coeff":
             self.pending = self.consumed = False

@@ -2,7 +2,7 @@
 
 Every other GPU test has one shape: create a plan, forward(), at most one operator, inverse(), throw the plan away.  An iterative
 solver keeps ONE plan and calls its entry points in any order, and that is where plan.cpp's lazy state lives: a soft threshold that
-a separable 2D SWT plan defers into its inverse (`pend_soft`) and the write-back such an inverse owes (`soft_consumed`).
+a separable 2D SWT plan defers into its inverse (`pending`) and the write-back such an inverse owes (`consumed`).
 
 C1  seeded random sequences (plan_model.sequences(): conditions checked without a GPU by test_plan_model_cpu.py) on the plans of
     plan_model.PLANS, through the C ABI and through the Python classes.  After every call: return value and state equal the

@@ -214,3 +214,77 @@ def test_betas_matter():
         assert pm.BETAS["above"] > d.max() and pm.BETAS["negative"] < 0 == pm.BETAS["zero"], spec
         assert 0.02 <= float((d > pm.BETAS["inside"]).mean()) <= 0.98, (spec, float((d > pm.BETAS["inside"]).mean()))
         assert float((d > pm.BETAS["below"]).mean()) >= 0.99, spec
+
+
+# ------------------------------------------------------------------------------------------- the library's table against the model
+# pypwt_amd/csrc/lazy_state.hpp, in the order of `enum class Entry`, and of its `Pending` and `Consumed`
+ENTRIES = ("forward", "inverse", "soft", "eager_threshold", "norms", "read_stats", "band_sweep", "add_wavelet", "get_coeff",
+           "coeff_ptr", "set_coeff", "set_image", "clone", "untouched")
+KEEP, APPLY, DROP, CONSUME = 0, 1, 2, 3
+C_KEEP, WRITE_BACK, C_DROP = 0, 1, 2
+ENTRY_OF_KIND = {
+    "forward": "forward", "inverse": "inverse", "soft": "soft", "soft_norms": "soft",
+    "hard": "eager_threshold", "group": "eager_threshold", "shrink": "eager_threshold", "linf": "eager_threshold",
+    "norm1": "norms", "norm2sq": "norms", "norms_async": "norms", "add_dst": "add_wavelet", "add_src": "add_wavelet",
+    "get_coeff": "get_coeff", "get_coeff_at": "get_coeff", "get_region": "get_coeff", "raw_read": "coeff_ptr",
+    "set_coeff": "set_coeff", "set_image": "set_image", "clone": "clone",
+    "get_image": "untouched", "get_image_at": "untouched", "circshift": "untouched", "filt_fwd": "untouched", "filt_inv": "untouched",
+}
+
+
+def test_the_librarys_lazy_state_table_is_the_models_and_the_documents():
+    """Every Entry of lazy_state.hpp (what plan.cpp's settle() performs) against plan_model.Situation, kind by kind and situation
+    by situation, and against the rows of docs/KERNELS.md for the entries the model has no kind for."""
+    import ctypes as C
+
+    import emu_util
+    lib = emu_util.lib()
+    rows, out = {}, (C.c_int * 3)()
+    for i, name in enumerate(ENTRIES):
+        assert lib.emu_lazy_row(i, out) == 0, name
+        rows[name] = tuple(out)
+    assert lib.emu_lazy_row(len(ENTRIES), out) == -1, "an Entry this test does not know"
+    assert not [k for k in pm.KINDS if k not in ENTRY_OF_KIND], "a kind of the model without an Entry"
+
+    def library(row, state, pending, consumed):
+        """(pending, consumed) after settle() and, for Pending::consume, the success branch of pdwt_inverse"""
+        refuses, p, c = row
+        if refuses and state == pm.INVERSE:
+            return True, pending, consumed
+        if p == CONSUME:
+            pending, consumed = False, consumed or pending
+        elif p in (APPLY, DROP):
+            pending = False
+        if c in (WRITE_BACK, C_DROP):
+            consumed = False
+        return False, pending, consumed
+
+    for kind in pm.KINDS:
+        row = rows[ENTRY_OF_KIND[kind]]
+        # soft / soft_norms with do_app: what the call owes the EARLIER threshold (without it the new one becomes pending, below)
+        op = {"soft": (kind, 12.0, 1, 0), "soft_norms": (kind, 12.0, 1, 0), "set_coeff": (kind, 1, 5)}.get(kind, (kind,))
+        for state in (pm.FORWARD, pm.INVERSE):
+            for pending, consumed in ((False, False), (True, False), (False, True)):
+                sit = pm.Situation()
+                sit.state, sit.pending, sit.consumed = state, pending, consumed
+                no = sit.would_refuse(kind, False)
+                sit.step(op, False)
+                want = library(row, state, pending, consumed)
+                if (kind, state, consumed) == ("inverse", pm.FORWARD, True):
+                    # The library reaches "consumed outside INVERSE" only through a failed un-shift (PDWT_INVERSE_ERROR), a state the
+                    # model does not have: there the stored details still owe the threshold and the row keeps it; the model's
+                    # inverse() assigns `consumed = pending`
+                    assert want == (False, False, True) and (no, sit.pending, sit.consumed) == (False, False, False)
+                    continue
+                assert (no, sit.pending, sit.consumed) == want, (kind, state, pending, consumed)
+    for kind in ("soft", "soft_norms"):  # the one place that defers: after the earlier threshold has been applied
+        for pending in (False, True):
+            sit = pm.Situation()
+            sit.pending = pending
+            sit.step((kind, 12.0, 0, 0), False)
+            assert sit.pending and not sit.consumed and rows["soft"][1] == APPLY
+
+    # the entries without a kind: the literal rows of docs/KERNELS.md
+    assert rows["read_stats"] == rows["norms"] == (0, APPLY, WRITE_BACK)
+    assert rows["band_sweep"][:2] == (1, APPLY)
+    assert rows["untouched"] == (0, KEEP, C_KEEP)
