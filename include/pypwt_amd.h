@@ -169,6 +169,29 @@ int pdwt_estimate_sigma_async(pdwt_handle h, int skip_zeros, double* d_out);
 int pdwt_threshold_bands(pdwt_handle h, int op, const pdwt_real* table, int table_on_device);
 int pdwt_denoise_async(pdwt_handle h, int method, int op, const double* sigma, int nsigma, int skip_zeros);
 int pdwt_adaptive_slots(pdwt_handle h, double** d_stats, double** d_sigma, pdwt_real** d_table);
+/* ---- NEW: best K-term approximation on the device (no reference counterpart: the reference's thresholds take a VALUE,
+ * wt.cu:308-325; here the caller fixes the sparsity).  Keep the K coefficients of largest magnitude of every image and zero
+ * the rest, as compression and iterative hard thresholding do.  Per image i: S = the swept bands (all detail bands, and band 0
+ * when do_thresh_appcoeffs != 0), N = their elements per image, key(c) = the bit pattern of |c| (NaNs order behind +inf,
+ * -0.0 == +0.0 == 0).  K[i] is clamped to [0, N].  K == 0: every element of S becomes +0.0, threshold +inf, kept 0.  K >= N:
+ * nothing changes, threshold 0, kept N.  Otherwise t = the element of ascending rank N - K among the keys -- the K-th largest
+ * magnitude, EXACT (the radix select of pdwt_estimate_sigma_async, over all swept bands) --; c stays, bit for bit, iff
+ * key(c) >= key(t), else it becomes +0.0: ties at t all survive, kept[i] = the elements with key >= key(t) >= K (== K without
+ * ties).  kept comes out of the select's walks, not out of the sweep: two calls give the same bits.  The padding behind a
+ * band is neither read nor written.  "Image" is what it is to pdwt_band_stats_async (the rows of a batched 1D plan are pooled).
+ * Refused with PDWT_ERR_UNSUPPORTED when N >= 2^32; the limits of the per-band operators apply.
+ * State rules: pdwt_select_magnitude_async takes what pdwt_band_stats_async takes; pdwt_keep_largest_async follows
+ * pdwt_threshold_bands -- PDWT_ERR_STATE after pdwt_inverse, nothing done, the plan's state unchanged.  PDWT_ERR_ARG: a null k,
+ * nk not in {1, batch}, a negative K. */
+/* t[i] = K[i]-th largest |c| over the swept bands of image i, kept[i] = elements with |c| >= t[i]; read-only, enqueued, no host wait.
+ * k: host memory, nk = 1 (one K for all images) or nk = batch.  d_threshold [batch] pdwt_real, d_kept [batch] unsigned long long:
+ * device memory, or NULL = the plan's own slots. */
+int pdwt_select_magnitude_async(pdwt_handle h, const long long* k, int nk, int do_thresh_appcoeffs,
+                                pdwt_real* d_threshold, unsigned long long* d_kept);
+/* the select above, then ONE read-modify-write sweep over the swept bands that keeps what the rule keeps */
+int pdwt_keep_largest_async(pdwt_handle h, const long long* k, int nk, int do_thresh_appcoeffs);
+/* device addresses of the plan's own slots of the last of the two calls (either argument may be NULL) */
+int pdwt_sparsify_slots(pdwt_handle h, pdwt_real** d_threshold, unsigned long long** d_kept);
 /* dst += alpha * src ; returns 0, or the reference's codes -1..-4 / +1 (wt.cu:622-655) */
 int pdwt_add_wavelet(pdwt_handle dst, pdwt_handle src, pdwt_real alpha);
 

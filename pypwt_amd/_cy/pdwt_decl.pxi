@@ -42,6 +42,11 @@ cdef extern from "pypwt_amd.h":
     int pdwt_threshold_bands(pdwt_handle h, int op, const float* table, int table_on_device)   # op 0 soft, 1 hard; NaN = untouched
     int pdwt_denoise_async(pdwt_handle h, int method, int op, const double* sigma, int nsigma, int skip_zeros)
     int pdwt_adaptive_slots(pdwt_handle h, double** d_stats, double** d_sigma, float** d_table)
+    # best K-term approximation on the device (no reference counterpart): the K-th largest |c| per image over the swept bands
+    # (exact), and the sweep that keeps what is at least as large; k in host memory, nk = 1 or batch; results stay in device memory
+    int pdwt_select_magnitude_async(pdwt_handle h, const long long* k, int nk, int do_app, float* d_threshold, unsigned long long* d_kept)
+    int pdwt_keep_largest_async(pdwt_handle h, const long long* k, int nk, int do_app)
+    int pdwt_sparsify_slots(pdwt_handle h, float** d_threshold, unsigned long long** d_kept)
     # data movement
     long long pdwt_get_image(pdwt_handle h, float* dst)                             # pypwt.pyx:52
     long long pdwt_get_coeff(pdwt_handle h, float* dst, int num)                    # pypwt.pyx:54

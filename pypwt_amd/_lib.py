@@ -66,6 +66,9 @@ def signatures(real=C.c_float):
         "pdwt_threshold_bands": (C.c_int, [handle_t, C.c_int, C.c_void_p, C.c_int]),
         "pdwt_denoise_async": (C.c_int, [handle_t, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int]),
         "pdwt_adaptive_slots": (C.c_int, [handle_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+        "pdwt_select_magnitude_async": (C.c_int, [handle_t, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+        "pdwt_keep_largest_async": (C.c_int, [handle_t, C.POINTER(C.c_longlong), C.c_int, C.c_int]),
+        "pdwt_sparsify_slots": (C.c_int, [handle_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
         "pdwt_add_wavelet": (C.c_int, [handle_t, handle_t, real]),
         "pdwt_get_image": (C.c_longlong, [handle_t, C.c_void_p]),
         "pdwt_get_coeff": (C.c_longlong, [handle_t, C.c_void_p, C.c_int]),

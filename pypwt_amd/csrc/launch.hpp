@@ -211,6 +211,17 @@ size_t select_state_bytes(int batch);
 size_t select_hist_bytes(int batch);
 hipError_t launch_select_hist(const real_t* band, long long n, int batch, int pass, void* state, unsigned* hist, hipStream_t s);
 hipError_t launch_select_walk(long long n, int batch, int pass, int skip_zeros, void* state, unsigned* hist, double* sigma, hipStream_t s);
+// the K-th largest |c| per image over the bands first_band .. of `t` (n values per image in all): the same passes with the
+// histogram sweep over the pieces of `t` and a walk for the rank n - k[image].  d_k: [batch] long long in device memory;
+// the last walk writes d_key[image] (select_key_bytes() each: what launch_keep_bands compares against), d_threshold[image]
+// and d_kept[image].  State and histograms are those of the median select and are left zero in the same way.
+size_t select_key_bytes();
+hipError_t launch_select_hist_bands(const real_t* arena, const BandTable& t, int first_band, int pass, const long long* d_k,
+                                    unsigned long long n, const void* state, unsigned* hist, hipStream_t s);
+hipError_t launch_select_walk_rank(int batch, int pass, const long long* d_k, unsigned long long n, void* state, unsigned* hist, void* d_key,
+                                   real_t* d_threshold, unsigned long long* d_kept, hipStream_t s);
+// x stays iff the bit pattern of |x| >= d_key[image], else +0.0, over the bands first_band .. of `t`, in ONE launch
+hipError_t launch_keep_bands(real_t* arena, const BandTable& t, int first_band, const void* d_key, hipStream_t s);
 hipError_t launch_circshift(const real_t* in, real_t* out, int batch, int Nr, int Nc, int sr, int sc, hipStream_t s);
 hipError_t launch_copy(const real_t* src, real_t* dst, long long n, hipStream_t s);  // 16-B grid-stride copy (n % 4 == 0)
 hipError_t launch_fill_hash(real_t* x, long long n, uint32_t seed, real_t scale, long long index_offset,

@@ -123,6 +123,30 @@ hipError_t launch_select_walk(long long n, int batch, int pass, int skip_zeros, 
     return hipGetLastError();
 }
 
+size_t select_key_bytes() { return sizeof(select_key_t); }
+
+hipError_t launch_select_hist_bands(const real_t* arena, const BandTable& t, int first_band, int pass, const long long* d_k,
+                                    unsigned long long n, const void* state, unsigned* hist, hipStream_t s) {
+    if (first_band < 0 || first_band >= t.nbands || t.blk[t.nbands] < 1 || pass < 0 || pass >= kSelectPasses) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(select_hist_bands_kernel, dim3(t.blk[t.nbands]), dim3(kSelectHistThreads), 0, s, arena, t, first_band, pass, d_k, n,
+                       static_cast<const SelectState*>(state), hist);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_walk_rank(int batch, int pass, const long long* d_k, unsigned long long n, void* state, unsigned* hist, void* d_key,
+                                   real_t* d_threshold, unsigned long long* d_kept, hipStream_t s) {
+    hipLaunchKernelGGL(select_walk_rank_kernel, dim3(batch), dim3(256), 0, s, pass, d_k, n, static_cast<SelectState*>(state), hist,
+                       static_cast<select_key_t*>(d_key), d_threshold, d_kept);
+    return hipGetLastError();
+}
+
+hipError_t launch_keep_bands(real_t* arena, const BandTable& t, int first_band, const void* d_key, hipStream_t s) {
+    const int blocks = t.blk[t.nbands];
+    if (blocks < 1 || first_band < 0 || first_band >= t.nbands) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((keep_bands_kernel<select_key_t>), dim3(blocks), dim3(256), 0, s, arena, t, first_band, static_cast<const select_key_t*>(d_key));
+    return hipGetLastError();
+}
+
 hipError_t launch_circshift(const real_t* in, real_t* out, int batch, int Nr, int Nc, int sr, int sc,
                             hipStream_t s) {
     const long long plane = (long long)Nr * Nc;

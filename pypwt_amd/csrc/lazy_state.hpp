@@ -16,8 +16,8 @@ enum class Entry {
     soft,             // soft_threshold, soft_threshold_norms
     eager_threshold,  // hard_threshold, group_soft_threshold, shrink, proj_linf
     norms,            // norm1, norm2sq, norms_async
-    read_stats,       // band_stats_async, estimate_sigma_async
-    band_sweep,       // threshold_bands, denoise_async
+    read_stats,       // band_stats_async, estimate_sigma_async, select_magnitude_async
+    band_sweep,       // threshold_bands, denoise_async, keep_largest_async
     add_wavelet,      // both operands
     get_coeff,        // get_coeff, get_coeff_at, get_coeff_region
     coeff_ptr,

@@ -21,6 +21,7 @@
 //   band_stats       sum|x|, sum x^2 of every image of every band
 //   threshold_bands  soft / hard with a threshold of its own per (band, image)
 //   denoise_table    BayesShrink / VisuShrink thresholds out of those sums and a noise level per image
+//   keep_bands       best K-term approximation: keep what is at least as large as a per-image order statistic, zero the rest
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -286,6 +287,40 @@ __global__ void __launch_bounds__(256) threshold_bands_kernel(real_t* __restrict
                     v.y = ew_apply<OP>(v.y, b);
                     v.z = ew_apply<OP>(v.z, b);
                     v.w = ew_apply<OP>(v.w, b);
+                    r = v;
+                });
+}
+
+// Best K-term approximation: x stays, bit for bit, iff the bit pattern of |x| is at least key[image]; else it becomes +0.0.
+// KEY is the unsigned integer of real_t's width (select_key_t of select_kernels.hpp, whose walk leaves key[image] in device
+// memory): NaNs order behind +inf, ties at the key all survive.  Pieces of the bands before `first_band` are left alone.  A
+// key of 0 keeps everything: the piece returns before it reads; a key with the sign bit set is reached by nothing: the piece
+// writes zeros without reading.
+template <typename KEY>
+__global__ void __launch_bounds__(256) keep_bands_kernel(real_t* __restrict__ arena, BandTable t, int first_band, const KEY* __restrict__ key) {
+    static_assert(sizeof(KEY) == sizeof(real_t), "the key is the bit pattern of a value");
+    int band, img;
+    long long a, e;
+    band_piece(t, blockIdx.x, &band, &img, &a, &e);
+    if (band < first_band) return;
+    const KEY k = key[img], mag = ~(KEY)0 >> 1;
+    if (k == 0) return;
+    if (k > mag) {
+        sweep_range(arena, a, e, [&](real_t& x) { x = real_t(0); }, [&](real4_t& r) { r = real4_t{real_t(0), real_t(0), real_t(0), real_t(0)}; });
+        return;
+    }
+    auto keep = [&](real_t x) {
+        KEY u;
+        __builtin_memcpy(&u, &x, sizeof(u));
+        return (u & mag) >= k ? x : real_t(0);
+    };
+    sweep_range(arena, a, e, [&](real_t& x) { x = keep(x); },
+                [&](real4_t& r) {
+                    real4_t v = r;
+                    v.x = keep(v.x);
+                    v.y = keep(v.y);
+                    v.z = keep(v.z);
+                    v.w = keep(v.w);
                     r = v;
                 });
 }

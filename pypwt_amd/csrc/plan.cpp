@@ -1272,12 +1272,13 @@ int ensure_adaptive(pdwt_plan* p) {
     if (B > 65535) return fail(PDWT_ERR_UNSUPPORTED, "per-band operators take at most 65535 images (this plan has %d)", B);
     AdaptiveWs* w = new AdaptiveWs();
     long long blocks = 0;
-    for (int which = 0; which < 2; which++) {
-        BandTable& t = which ? w->bt_stats : w->bt;
+    for (int which = 0; which < 3; which++) {
+        BandTable& t = which == 0 ? w->bt : which == 1 ? w->bt_stats : w->bt_hist;
         t.nbands = nb;
         t.batch = B;
         t.chunk = cdivll(cdivll(p->coeff_elems, which ? 1024 : 2048), 1024) * 1024;
-        if (t.chunk < 4096) t.chunk = 4096;
+        // (a histogram workgroup zeroes and flushes a 32-KiB LDS histogram: launch_ops.hip, select_chunk)
+        if (t.chunk < (which == 2 ? 8192 : 4096)) t.chunk = which == 2 ? 8192 : 4096;
         long long n_blocks = 0;
         for (int k = 0; k < nb; k++) {
             t.off[k] = p->bands[k].off;
@@ -1290,14 +1291,19 @@ int ensure_adaptive(pdwt_plan* p) {
             }
         }
         t.blk[nb] = (int)n_blocks;
-        if (which) blocks = n_blocks;
+        if (which == 1) blocks = n_blocks;
     }
     const size_t sz_stats = align256((size_t)2 * nb * B * sizeof(double)), sz_sigma = align256((size_t)B * sizeof(double)),
                  sz_table = align256((size_t)nb * B * sizeof(real_t)), sz_part = align256((size_t)2 * blocks * sizeof(double)),
-                 sz_state = align256(select_state_bytes(B)), sz_hist = align256(select_hist_bytes(B));
-    hipError_t e = pool_alloc(p->device, &w->block, sz_stats + sz_sigma + sz_table + sz_part + sz_state + sz_hist, &w->bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(w->block, 0, sz_stats + sz_sigma + sz_table + sz_part + sz_state + sz_hist, p->stream);
-    if (e == hipSuccess) e = hipHostMalloc(&w->h_stage, (size_t)nb * B * sizeof(real_t) + (size_t)B * sizeof(double), hipHostMallocDefault);
+                 sz_state = align256(select_state_bytes(B)), sz_hist = align256(select_hist_bytes(B)),
+                 sz_k = align256((size_t)B * sizeof(long long)), sz_key = align256((size_t)B * select_key_bytes()),
+                 sz_thr = align256((size_t)B * sizeof(real_t)), sz_kept = align256((size_t)B * sizeof(unsigned long long)),
+                 sz_all = sz_stats + sz_sigma + sz_table + sz_part + sz_state + sz_hist + sz_k + sz_key + sz_thr + sz_kept;
+    hipError_t e = pool_alloc(p->device, &w->block, sz_all, &w->bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(w->block, 0, sz_all, p->stream);
+    if (e == hipSuccess)
+        e = hipHostMalloc(&w->h_stage, (size_t)nb * B * sizeof(real_t) + (size_t)B * sizeof(double) + (size_t)B * sizeof(long long),
+                          hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&w->staged, hipEventDisableTiming);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -1313,6 +1319,11 @@ int ensure_adaptive(pdwt_plan* p) {
     w->partial = reinterpret_cast<double*>(base + sz_stats + sz_sigma + sz_table);
     w->sel_state = base + sz_stats + sz_sigma + sz_table + sz_part;
     w->sel_hist = reinterpret_cast<unsigned*>(base + sz_stats + sz_sigma + sz_table + sz_part + sz_state);
+    char* sp = base + sz_stats + sz_sigma + sz_table + sz_part + sz_state + sz_hist;
+    w->sp_k = reinterpret_cast<long long*>(sp);
+    w->sp_key = sp + sz_k;
+    w->sp_threshold = reinterpret_cast<real_t*>(sp + sz_k + sz_key);
+    w->sp_kept = reinterpret_cast<unsigned long long*>(sp + sz_k + sz_key + sz_thr);
     p->adaptive = w;
     return PDWT_OK;
 }
@@ -1370,6 +1381,47 @@ int estimate_sigma_impl(pdwt_plan* p, int skip_zeros, double* d_out) {
 int threshold_bands_impl(pdwt_plan* p, int op, const real_t* d_table) {
     Stamp st(p, "threshold_bands");
     HIP_TRY(launch_threshold_bands(op, p->arena, p->adaptive->bt, d_table, p->stream));
+    return PDWT_OK;
+}
+
+// Best K-term approximation.  The swept bands are first .. nbands - 1 (first = 0 with the approximation, else 1); n = their
+// elements per image.  The K's go to the device through the staging buffer (behind the table and the noise levels), the
+// passes read them there: nothing waits for the host.
+int sparsify_check(pdwt_plan* p, const char* what, const long long* k, int nk) {
+    if (!k) return fail(PDWT_ERR_ARG, "%s: null k", what);
+    if (nk != 1 && nk != p->batch) return fail(PDWT_ERR_ARG, "%s: %d values of K for %d images (one, or one per image)", what, nk, p->batch);
+    for (int i = 0; i < nk; i++)
+        if (k[i] < 0) return fail(PDWT_ERR_ARG, "%s: K = %lld is negative", what, k[i]);
+    return PDWT_OK;
+}
+
+int select_magnitude_impl(pdwt_plan* p, const char* what, const long long* k, int nk, int do_app, real_t* d_threshold,
+                          unsigned long long* d_kept) {
+    AdaptiveWs* w = p->adaptive;
+    const int B = p->batch, first = do_app ? 0 : 1;
+    unsigned long long n = 0;
+    for (int b = first; b < w->bt.nbands; b++) n += (unsigned long long)w->bt.n[b];
+    if (n >= (1ULL << 32)) return fail(PDWT_ERR_UNSUPPORTED, "%s: %llu swept elements per image (the histogram bins are 32-bit)", what, n);
+    if (w->bt.nbands <= first) return fail(PDWT_ERR_UNSUPPORTED, "%s: the plan has no detail band", what);
+    std::vector<long long> per((size_t)B);
+    for (int i = 0; i < B; i++) per[i] = k[nk == 1 ? 0 : i];
+    const int rc = stage_upload(p, w->sp_k, per.data(), per.size() * sizeof(long long),
+                                (size_t)w->bt.nbands * B * sizeof(real_t) + (size_t)B * sizeof(double));
+    if (rc != PDWT_OK) return rc;
+    for (int pass = 0; pass < select_passes(); pass++) {
+        char name[32];
+        {
+            snprintf(name, sizeof(name), "select_hist_bands%d", pass);
+            Stamp st(p, name);
+            HIP_TRY(launch_select_hist_bands(p->arena, w->bt_hist, first, pass, w->sp_k, n, w->sel_state, w->sel_hist, p->stream));
+        }
+        {
+            snprintf(name, sizeof(name), "select_walk_rank%d", pass);
+            Stamp st(p, name);
+            HIP_TRY(launch_select_walk_rank(B, pass, w->sp_k, n, w->sel_state, w->sel_hist, w->sp_key, d_threshold ? d_threshold : w->sp_threshold,
+                                            d_kept ? d_kept : w->sp_kept, p->stream));
+        }
+    }
     return PDWT_OK;
 }
 
@@ -1737,6 +1789,41 @@ int pdwt_denoise_async(pdwt_handle h, int method, int op, const double* sigma, i
         HIP_TRY(launch_denoise_table(w->bt, w->stats, w->sigma, method, visu, w->table, h->stream));
     }
     return threshold_bands_impl(h, op, w->table);
+}
+
+// ---------------------------------------------------------------- NEW: best K-term approximation (no reference counterpart)
+// The select reads what a reader of the coefficients would see (Entry::read_stats); the sweep follows pdwt_threshold_bands
+// (Entry::band_sweep).  Its pieces cover the bands' own values only: the padding is neither read nor written.
+int pdwt_select_magnitude_async(pdwt_handle h, const long long* k, int nk, int do_thresh_appcoeffs, real_t* d_threshold,
+                                unsigned long long* d_kept) {
+    CHECK_HANDLE(h);
+    if (const int rc = sparsify_check(h, "select_magnitude", k, nk)) return rc;
+    PDWT_ENTER(h, Entry::read_stats);
+    const int rc = ensure_adaptive(h);
+    return rc != PDWT_OK ? rc : select_magnitude_impl(h, "select_magnitude", k, nk, do_thresh_appcoeffs, d_threshold, d_kept);
+}
+
+int pdwt_keep_largest_async(pdwt_handle h, const long long* k, int nk, int do_thresh_appcoeffs) {
+    CHECK_HANDLE(h);
+    if (const int rc = sparsify_check(h, "keep_largest", k, nk)) return rc;
+    PDWT_ENTER_OR(h, Entry::band_sweep,
+                  fail(PDWT_ERR_STATE, "keep_largest: cannot threshold coefficients, as they were modified by inverse()"));
+    int rc = ensure_adaptive(h);
+    if (rc == PDWT_OK) rc = select_magnitude_impl(h, "keep_largest", k, nk, do_thresh_appcoeffs, nullptr, nullptr);
+    if (rc != PDWT_OK) return rc;
+    Stamp st(h, "keep_bands");
+    HIP_TRY(launch_keep_bands(h->arena, h->adaptive->bt, do_thresh_appcoeffs ? 0 : 1, h->adaptive->sp_key, h->stream));
+    return PDWT_OK;
+}
+
+int pdwt_sparsify_slots(pdwt_handle h, real_t** d_threshold, unsigned long long** d_kept) {
+    CHECK_HANDLE(h);
+    DeviceGuard guard(h->device);
+    const int rc = ensure_adaptive(h);
+    if (rc != PDWT_OK) return rc;
+    if (d_threshold) *d_threshold = h->adaptive->sp_threshold;
+    if (d_kept) *d_kept = h->adaptive->sp_kept;
+    return PDWT_OK;
 }
 
 int pdwt_adaptive_slots(pdwt_handle h, double** d_stats, double** d_sigma, real_t** d_table) {

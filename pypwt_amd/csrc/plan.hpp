@@ -49,7 +49,8 @@ struct KernelStamp {
     char family[16];  // which of a step's alternative kernels ran (launch.hpp: note_family); "" when the step has only one
 };
 
-// Device workspace of the per-band operators (band_stats, estimate_sigma, threshold_bands, denoise): ONE block, allocated
+// Device workspace of the per-band operators (band_stats, estimate_sigma, threshold_bands, denoise, select_magnitude,
+// keep_largest): ONE block, allocated
 // by the first of them that is called, so that plans that never call them keep their footprint (plan.cpp: ensure_adaptive)
 struct AdaptiveWs {
     void* block = nullptr;
@@ -60,9 +61,15 @@ struct AdaptiveWs {
     double* partial = nullptr;  // per-workgroup partial sums of band_stats
     void* sel_state = nullptr;  // radix select: per-image state and histogram (select_kernels.hpp)
     unsigned* sel_hist = nullptr;
+    // best K-term approximation (select_magnitude, keep_largest), all [batch]
+    long long* sp_k = nullptr;               // the K of every image as the caller gave it
+    void* sp_key = nullptr;                  // the selected key (select_key_t): what the keep sweep compares against
+    real_t* sp_threshold = nullptr;          // ... as a value
+    unsigned long long* sp_kept = nullptr;   // elements with |c| >= the threshold
     BandTable bt{};        // the sweep of threshold_bands: about 2048 pieces, the grid of the whole-arena maps
     BandTable bt_stats{};  // ... of band_stats: about 1024, the grid of the whole-arena norms
-    // pinned host staging of a table / of noise levels the caller passes in host memory, and the event behind its last upload
+    BandTable bt_hist{};   // ... of the rank select's histogram passes: about 1024 of 8192 values at least (1024 threads each)
+    // pinned host staging of a table / of noise levels / of the K's the caller passes in host memory, and the event behind its last upload
     void* h_stage = nullptr;
     hipEvent_t staged = nullptr;
 };

@@ -11,6 +11,12 @@
 //                        and remaining rank in device memory for the next pass.
 // No host round trip between passes.
 //
+// The same passes select ANY rank (best K-term approximation: the K-th largest |c| over several bands of an image):
+//   select_hist_bands_kernel  the histogram sweep over the pieces of a BandTable, every piece into the histogram of ITS image;
+//   select_walk_rank_kernel   the walk for the ascending rank N - K[image] instead of the median ranks; it also adds up how
+//                             many elements lie BELOW the bucket it descends into, so that after the last pass N minus that
+//                             sum is the number of elements with key >= the selected one -- ties included, no second sweep.
+//
 // The median of an even count needs the ranks r and r + 1, which may part in any pass.  Only r is selected.  While r + 1
 // lies in the same bucket it shares the prefix (hi_mode 0); when it does not, it is the SMALLEST element of the next
 // non-empty bucket, and from then on the histogram sweep also keeps the minimum digit under that second prefix (hi_mode 1):
@@ -53,6 +59,7 @@ struct SelectState {
     unsigned hi_min;               // hi_mode 1: smallest digit of this pass under hi_prefix, min'ed by the histogram sweep
     int hi_mode;                   // 0: the upper element shares lo's bucket; 1: it is the minimum under hi_prefix; 2: it IS lo
     int empty;                     // no element takes part: the result is 0
+    unsigned long long below;      // rank select: elements whose key is smaller than every key under lo_prefix, over the passes
 };
 
 PDWT_DEVICE int select_pass_bits(int pass) {
@@ -198,6 +205,58 @@ PDWT_DEVICE double select_median(const SelectState& st) {
     return (a + (double)select_value(hi)) * 0.5;
 }
 
+// ---- a given rank: the K-th largest of n elements (K from the caller, any value >= 0)
+constexpr int kSelectKeepAll = 1;   // K >= n: every element is "at least as large", the threshold is 0
+constexpr int kSelectKeepNone = 2;  // K == 0: no element is, the threshold is +inf
+// a key that no element reaches (the sign bit is never set in a key): what the keep sweep compares against when K == 0
+constexpr select_key_t kSelectKeyNone = ~(select_key_t)0;
+
+// K clamped to [0, n]; the two ends need no pass at all
+PDWT_DEVICE int select_rank_flag(long long k, unsigned long long n) {
+    if (k <= 0) return kSelectKeepNone;
+    return (unsigned long long)k >= n ? kSelectKeepAll : 0;
+}
+
+// One pass's walk for the K-th largest of n elements, i.e. ascending rank n - K: as select_step, without the second middle
+// element and without the zeros, and with the count of what lies below the chosen bucket added up in st.below.
+PDWT_DEVICE void select_rank_step(SelectState& st, int pass, const unsigned* h, const unsigned* part, const unsigned* part16, long long k,
+                                  unsigned long long n) {
+    const int bits = select_pass_bits(pass), bins = 1 << bits;
+    if (pass == 0) {
+        st.lo_prefix = st.hi_prefix = 0;
+        st.count = n;
+        st.empty = select_rank_flag(k, n) != 0;
+        st.lo_rank = st.empty ? 0 : n - (unsigned long long)k;
+        st.hi_mode = 2;
+        st.below = 0;
+    }
+    if (st.empty) return;
+    unsigned long long below = 0;
+    const int bin = select_descend(h, part, part16, bins, st.lo_rank, &below);
+    st.lo_prefix = (st.lo_prefix << bits) | (unsigned)bin;
+    st.lo_rank -= below;
+    st.below += below;
+}
+
+// after the last pass: the key of the K-th largest element and the number of elements whose key is at least that
+PDWT_DEVICE select_key_t select_rank_result(const SelectState& st, long long k, unsigned long long n, unsigned long long* kept) {
+    const int flag = select_rank_flag(k, n);
+    if (flag == kSelectKeepNone) {
+        *kept = 0;
+        return kSelectKeyNone;
+    }
+    if (flag == kSelectKeepAll) {
+        *kept = n;
+        return 0;
+    }
+    *kept = n - st.below;
+    return (select_key_t)st.lo_prefix;
+}
+// the threshold a caller sees: the element itself, +inf when nothing is kept
+PDWT_DEVICE real_t select_rank_value(select_key_t key) {
+    return key == kSelectKeyNone ? (real_t)__builtin_inf() : select_value(key);
+}
+
 constexpr double kSigmaDenominator = 0.6744897501960817;  // the 75 % quantile of the standard normal distribution
 
 #ifndef PDWT_CPU_EMU
@@ -279,6 +338,81 @@ __global__ void __launch_bounds__(256) select_walk_kernel(int pass, long long n,
         select_step(st, pass, h, part, part16, n, skip_zeros);
         if (pass == kSelectPasses - 1) {
             sigma[img] = select_median(st) / kSigmaDenominator;
+            st = SelectState{};
+        }
+        state[img] = st;
+    }
+}
+
+// The histogram sweep over SEVERAL bands: grid = the pieces of `t` (band_piece), 1024 threads; the pieces of the bands before
+// `first_band` return before they read, every other piece adds to the histogram of its image.  k[image]: the wanted K;
+// n: elements swept per image.  An image whose K needs no pass (0, or n and more) is not read at all.
+__global__ void __launch_bounds__(kSelectHistThreads) select_hist_bands_kernel(const real_t* __restrict__ arena, BandTable t, int first_band,
+                                                                               int pass, const long long* __restrict__ k, unsigned long long n,
+                                                                               const SelectState* __restrict__ state,
+                                                                               unsigned* __restrict__ hist) {
+    __shared__ unsigned lh[kSelectLdsWords];
+    int band, img;
+    long long a, e;
+    band_piece(t, blockIdx.x, &band, &img, &a, &e);
+    if (band < first_band) return;
+    select_key_t lo_prefix = 0;
+    if (pass == 0) {
+        if (select_rank_flag(k[img], n)) return;
+    } else {
+        if (state[img].empty) return;
+        lo_prefix = (select_key_t)state[img].lo_prefix;
+    }
+    const int bits = select_pass_bits(pass), shift = select_pass_shift(pass), bins = 1 << bits;
+    const int copies = kSelectLdsWords >> bits, copy = threadIdx.x & (copies - 1);  // as select_hist_kernel
+    for (int i = threadIdx.x; i < kSelectLdsWords; i += kSelectHistThreads) lh[i] = 0;
+    __syncthreads();
+    unsigned unused = kSelectNoDigit;
+    auto one = [&](real_t x) {
+        const int d = select_classify(select_key(x), shift, bits, lo_prefix, 0, 0, &unused);
+        if (d >= 0) atomicAdd(&lh[d * copies + copy], 1u);
+    };
+    sweep_range(arena, a, e, one, [&](const real4_t& v) {
+        one(v.x);
+        one(v.y);
+        one(v.z);
+        one(v.w);
+    });
+    __syncthreads();
+    for (int b = threadIdx.x; b < bins; b += kSelectHistThreads) {
+        unsigned s = 0;
+        for (int c = 0; c < copies; c++) s += lh[b * copies + c];
+        if (s) atomicAdd(&hist[(long long)img * kSelectMaxBins + b], s);
+    }
+}
+
+// one workgroup per image, as select_walk_kernel; the last pass writes key[image] (what the keep sweep compares against),
+// threshold[image], kept[image] and clears the image's state
+__global__ void __launch_bounds__(256) select_walk_rank_kernel(int pass, const long long* __restrict__ k, unsigned long long n,
+                                                               SelectState* __restrict__ state, unsigned* __restrict__ hist,
+                                                               select_key_t* __restrict__ key, real_t* __restrict__ threshold,
+                                                               unsigned long long* __restrict__ kept) {
+    __shared__ unsigned h[kSelectMaxBins], part[256], part16[16];
+    const int img = blockIdx.x, bins = 1 << select_pass_bits(pass);
+    unsigned* gh = hist + (long long)img * kSelectMaxBins;
+    for (int b = threadIdx.x; b < bins; b += 256) {
+        h[b] = gh[b];
+        gh[b] = 0;
+    }
+    __syncthreads();
+    part[threadIdx.x] = select_part_sum(h, bins, threadIdx.x);
+    __syncthreads();
+    if (threadIdx.x < 16) part16[threadIdx.x] = select_part16_sum(part, threadIdx.x);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        SelectState st = state[img];
+        select_rank_step(st, pass, h, part, part16, k[img], n);
+        if (pass == kSelectPasses - 1) {
+            unsigned long long cnt;
+            const select_key_t res = select_rank_result(st, k[img], n, &cnt);
+            key[img] = res;
+            threshold[img] = select_rank_value(res);
+            kept[img] = cnt;
             st = SelectState{};
         }
         state[img] = st;

@@ -110,7 +110,10 @@ class _AdaptiveOps(object):
     median of the noise band, one threshold per (band, image) in one sweep, and the BayesShrink / VisuShrink recipes of
     ``skimage.restoration.denoise_wavelet`` on top of them.  Shared by ``Wavelets`` (one image) and ``BatchedWavelets``; "band" is
     the index of ``coeff_only``, the noise band is D1 (band 3 in 2D, band 1 in 1D).  Everything is enqueued on the plan's stream
-    and not waited for; results stay in device memory until a ``read_*`` / ``last_thresholds`` call copies them."""
+    and not waited for; results stay in device memory until a ``read_*`` / ``last_thresholds`` call copies them.
+
+    Also NEW: the best K-term approximation -- ``select_magnitude`` / ``keep_largest`` / ``last_sparsify`` fix the sparsity
+    instead of the threshold (the K-th largest magnitude per image by the same exact select, over all swept bands)."""
 
     _DENOISE_METHODS = {"bayesshrink": 0, "visushrink": 1}
     _THRESHOLD_MODES = {"soft": 0, "hard": 1}
@@ -231,6 +234,70 @@ class _AdaptiveOps(object):
         _, sg, tb = self._adaptive_slots()
         return (_read_device(self._lib, self._h, sg, (batch,), np.float64),
                 _read_device(self._lib, self._h, tb, (nb, batch), self._dtype))
+
+    # ---------------------------------------------------------------- best K-term approximation (NEW, no reference counterpart)
+    def _sparsify_slots(self):
+        th, kp = C.c_void_p(), C.c_void_p()
+        check(self._lib.pdwt_sparsify_slots(self._h, C.byref(th), C.byref(kp)), "pdwt_sparsify_slots", self._lib)
+        return th.value, kp.value
+
+    def _sparsify_count(self, do_threshold_appcoeffs):
+        """N: the elements per image of the swept bands (the detail bands, and the approximation when asked for)."""
+        nb, batch = self._adaptive_dims()
+        first = 0 if do_threshold_appcoeffs else 1
+        return sum(check(int(self._lib.pdwt_coeff_count(self._h, num, None, None)), "", self._lib) for num in range(first, nb)) // batch
+
+    def _sparsify_k(self, what, k, fraction, do_threshold_appcoeffs):
+        """(k as a contiguous int64 array of 1 or batch values, its C argument) out of exactly one of ``k`` and ``fraction``."""
+        batch = self._adaptive_dims()[1]
+        expected = "%s: expected exactly one of k (an int >= 0, or %d ints, one per image) and fraction (a number in [0, 1])" % (what, batch)
+        if (k is None) == (fraction is None):
+            raise ValueError(expected)
+        if fraction is not None:
+            try:
+                f = float(fraction)
+            except (TypeError, ValueError):
+                raise ValueError(expected + ", got fraction=%r" % (fraction,))
+            if not 0.0 <= f <= 1.0:  # a NaN fails both comparisons
+                raise ValueError(expected + ", got fraction=%r" % (fraction,))
+            ks = np.array([int(round(f * self._sparsify_count(do_threshold_appcoeffs)))], dtype=np.int64)
+        else:
+            try:
+                arr = np.asarray(k)
+                if arr.dtype.kind not in "iu" or arr.ndim > 1 or arr.size not in (1, batch):
+                    raise ValueError
+                if arr.size and (arr.dtype.kind == "u" and arr.max() > np.iinfo(np.int64).max or arr.min() < 0):
+                    raise ValueError
+            except (TypeError, ValueError):
+                raise ValueError(expected + ", got k=%r" % (k,))
+            ks = np.ascontiguousarray(arr.reshape(-1), dtype=np.int64)
+        return ks, ks.ctypes.data_as(C.POINTER(C.c_longlong))
+
+    def select_magnitude(self, k=None, fraction=None, do_threshold_appcoeffs=0):
+        """The K-th largest ``|c|`` of every image over the detail bands (and the approximation with ``do_threshold_appcoeffs``),
+        EXACT, and how many elements are at least that large: ``(threshold, kept)`` as device views of the plan's slots, (batch,)
+        of the instance's dtype and (batch,) uint64.  ``k``: an int or one per image; ``fraction``: K = round(fraction * N).
+        Read-only; ``last_sparsify`` copies the pair to the host.  K = 0 gives (+inf, 0), K >= N gives (0, N)."""
+        ks, arg = self._sparsify_k("select_magnitude", k, fraction, do_threshold_appcoeffs)
+        check(self._lib.pdwt_select_magnitude_async(self._h, arg, int(ks.size), 1 if do_threshold_appcoeffs else 0, None, None),
+              "select_magnitude", self._lib)
+        batch = self._adaptive_dims()[1]
+        th, kp = self._sparsify_slots()
+        return self._adaptive_view(th, (batch,), self._dtype), self._adaptive_view(kp, (batch,), np.uint64)
+
+    def keep_largest(self, k=None, fraction=None, do_threshold_appcoeffs=0):
+        """Best K-term approximation: keep, bit for bit, the K coefficients of largest magnitude of every image (ties with the
+        K-th all survive; NaNs count as larger than +inf) and set the rest to +0.0 -- the select above and one sweep, nothing
+        through the host.  After ``inverse()`` it warns and does nothing, like every threshold."""
+        ks, arg = self._sparsify_k("keep_largest", k, fraction, do_threshold_appcoeffs)
+        self._refused(self._lib.pdwt_keep_largest_async(self._h, arg, int(ks.size), 1 if do_threshold_appcoeffs else 0))
+
+    def last_sparsify(self):
+        """(threshold, kept) of the last ``select_magnitude`` / ``keep_largest``, copied to the host (waits for the plan's
+        stream): (batch,) of the instance's dtype and (batch,) uint64."""
+        batch = self._adaptive_dims()[1]
+        th, kp = self._sparsify_slots()
+        return _read_device(self._lib, self._h, th, (batch,), self._dtype), _read_device(self._lib, self._h, kp, (batch,), np.uint64)
 
 
 class Wavelets(_AdaptiveOps):

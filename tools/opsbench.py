@@ -45,7 +45,7 @@ for shape, wname, L, swt in (((4096, 4096), "db4", 4, 0), ((2048, 2048), "haar",
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The per (band, image) operators (band_stats, estimate_sigma, threshold_bands, denoise) next to the whole-arena sweeps that
+# The per (band, image) operators (band_stats, estimate_sigma, threshold_bands, denoise; select_magnitude, keep_largest) next to the whole-arena sweeps that
 # move the same bytes, on the default config's plans (4096^2 db4 L4, batch 1 and 16) and the SWT config's (2048^2 haar L5).
 # Hash input: the detail bands are noise-like, which is what the first pass of the select has to cope with.
 from collections import defaultdict
@@ -94,5 +94,51 @@ for batch, N, wname, L, swt in ((1, 4096, "db4", 4, 0), (16, 4096, "db4", 4, 0),
         us = float(np.median(acc[name]))
         rate = "  %7.0f GB/s read" % (4 * nnoise / us / 1e3) if name.startswith("select_hist") else ""
         print("  %-22s %8.1f us%s" % (name, us, rate))
+    B.enable_kernel_timing(False)
+
+    # ---- best K-term approximation (select_magnitude, keep_largest) next to the parent operators with the same inner loops, in
+    # the SAME run: every row three times (median, min-max: the run-to-run spread a difference has to exceed).  K = 10 % of the
+    # detail coefficients.  keep_largest zeroes 90 % of them, so "keep_largest (repeated)" selects on sparse data from the second
+    # call on (most elements in ONE first-pass bin); "forward + ..." feeds fresh coefficients every call.
+    def t3(fn):
+        r = sorted(t(fn, B.synchronize, 30) for _ in range(3))
+        return r[1], r[0], r[2]
+
+    print("# sparsify: K = N / 10, N = %d detail coefficients per image" % (ndet // batch))
+    for name, fn, nbytes in (
+        ("hard_threshold", lambda: B._lib.pdwt_hard_threshold(B._h, 1e-3, 0, 0), 8 * ndet),
+        ("estimate_sigma", B.estimate_sigma, 4 * nnoise * 3),
+        ("select_magnitude", lambda: B.select_magnitude(fraction=0.1), 4 * ndet * 3),
+        ("forward", B.forward, 0),
+        ("forward+hard_threshold", lambda: (B.forward(), B._lib.pdwt_hard_threshold(B._h, 1e-3, 0, 0)), 0),
+        ("forward+keep_largest", lambda: (B.forward(), B.keep_largest(fraction=0.1)), 0),
+        ("keep_largest (repeated)", lambda: B.keep_largest(fraction=0.1), 4 * ndet * 3 + 8 * ndet),
+    ):
+        B.forward()
+        us, lo, hi = t3(fn)
+        print("  %-24s %8.1f us  (%.1f - %.1f)" % (name, us, lo, hi) + ("  %7.0f GB/s" % (nbytes / us / 1e3) if nbytes else ""))
+    # pass by pass, event-timed, on fresh coefficients: the select over all detail bands next to the one over the noise band,
+    # the keep sweep next to the parent's hard_threshold sweep
+    B.enable_kernel_timing(True)
+    B.reset_kernel_times()
+    for _ in range(20):
+        B.forward()
+        B.estimate_sigma()
+        B._lib.pdwt_hard_threshold(B._h, 1e-3, 0, 0)
+        B.forward()
+        B.keep_largest(fraction=0.1)
+    B.synchronize()
+    acc = defaultdict(list)
+    for name, ms in B.kernel_times():
+        acc[name].append(ms * 1e3)
+    for name in sorted(acc):
+        if not (name.startswith("select_") or name in ("keep_bands", "hard_threshold")):
+            continue
+        v = np.sort(np.array(acc[name]))
+        us = float(np.median(v))
+        nbytes = 4 * ndet if name.startswith("select_hist_bands") else 4 * nnoise if name.startswith("select_hist") else \
+            8 * ndet if name in ("keep_bands", "hard_threshold") else 0
+        rate = "  %7.0f GB/s" % (nbytes / us / 1e3) if nbytes else ""
+        print("  %-24s %8.1f us  (%.1f - %.1f, quartiles)%s" % (name, us, v[len(v) // 4], v[(3 * len(v)) // 4], rate))
     B.enable_kernel_timing(False)
     del B
