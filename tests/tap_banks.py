@@ -1,0 +1,85 @@
+"""Filter banks whose every tap counts, and the tolerance that resolves them (tests/test_tap_banks_cpu.py, tests/test_gpu_taps.py).
+
+The built-in long wavelets have taps far below what an absolute tolerance of 2e-6 (1 + L) max(|band|, 255) can see (db20: 9 of 40 taps
+of dec_lo, the smallest 2e-10), so a kernel that dropped one would pass.  bank(n, seed) draws four INDEPENDENT filters of n taps, every
+tap sign * u / sqrt(n) with u uniform in [0.5, 1]: no tap below 0.5 / sqrt(40) = 0.079, an L2 norm of at most 1 per filter (three levels
+stay far from fp32 overflow), no quadrature-mirror structure a kernel could lean on or a forward bug could cancel against.
+
+The tolerance comes from the reference alone: the oracle runs twice with the same bank, in fp32 arithmetic and with fp64 accumulation
+on fp32 data; noise = max |f32 - f64acc| per band is the size of the error a correct fp32 evaluation makes (the kernels differ from
+the fp32 oracle in summation order and fma contraction only).  A kernel is compared with the f64acc result at K * noise, floored at
+one fp32 ulp of the band's maximum.
+
+K = 4.  The largest err / noise measured on the MI355X is 2.50 (the inverse strip kernels; every family and direction:
+profiles/taps_parity.txt), so 4 holds.  (K may be raised to twice the largest ratio a correct kernel needs, never beyond 16;
+tests/test_tap_banks_cpu.py demands that zeroing any single tap still moves the oracle by 1000 x the tolerance, whatever K is.)"""
+import numpy as np
+
+from oracle import oracle
+
+K = 4.0
+K_MAX = 16.0
+assert K <= K_MAX
+
+
+def bank(n, seed):
+    """(n, dec_lo, dec_hi, rec_lo, rec_hi) as float32: every tap sign * u / sqrt(n), u uniform in [0.5, 1]."""
+    rng = np.random.default_rng([int(n), int(seed)])
+    taps = []
+    for _ in range(4):
+        u = rng.uniform(0.5, 1.0, n)
+        sign = np.where(rng.integers(0, 2, n) == 1, 1.0, -1.0)
+        taps.append((sign * u / np.sqrt(n)).astype(np.float32))
+    return (int(n),) + tuple(taps)
+
+
+def without_tap(filt, which, j):
+    """The bank with tap j of filter `which` (1 dec_lo, 2 dec_hi, 3 rec_lo, 4 rec_hi) set to zero."""
+    out = [filt[0]] + [f.copy() for f in filt[1:]]
+    out[which][j] = 0
+    return tuple(out)
+
+
+def _tol(ref, f32, k):
+    noise = float(np.abs(f32.astype(np.float64) - ref).max())
+    floor = float(np.spacing(np.float32(np.abs(ref).max())))
+    return max(k * noise, floor), noise
+
+
+def forward_reference(x, levels, filt, ndim=2, do_swt=0, k=None):
+    """The f64acc oracle's bands of x, and per band (tolerance, noise): noise = max |fp32 oracle - f64acc oracle|."""
+    k = K if k is None else k
+    ref = oracle.forward(x, None, levels, ndim=ndim, do_swt=do_swt, double=True, filt=filt)
+    f32 = oracle.forward(x, None, levels, ndim=ndim, do_swt=do_swt, double=False, filt=filt)
+    return ref, [_tol(r, f, k) for r, f in zip(ref, f32)]
+
+
+def inverse_reference(bands, shape, levels, filt, ndim=2, do_swt=0, k=None):
+    """The f64acc oracle's synthesis of `bands` (fp32 arrays, e.g. forward_reference's), and its (tolerance, noise)."""
+    k = K if k is None else k
+    ref = oracle.inverse(bands, shape, None, levels, ndim=ndim, do_swt=do_swt, double=True, filt=filt)
+    f32 = oracle.inverse(bands, shape, None, levels, ndim=ndim, do_swt=do_swt, double=False, filt=filt)
+    return ref, _tol(ref, f32, k)
+
+
+def assert_forward(bands, x, levels, filt, cap, tag, ndim=2, do_swt=0):
+    """Kernel bands (flat list, the oracle's order) against forward_reference at its tolerance, `cap` * max(|band|, 1) at the most;
+    returns the reference bands."""
+    ref, tols = forward_reference(x, levels, filt, ndim=ndim, do_swt=do_swt)
+    assert len(bands) == len(ref), tag
+    for k, (g, r, (tol, noise)) in enumerate(zip(bands, ref, tols)):
+        err = float(np.abs(np.asarray(g).reshape(r.shape).astype(np.float64) - r).max())
+        assert err <= min(tol, cap * max(float(np.abs(r).max()), 1.0)), (tag, k, err, tol, noise)
+    return ref
+
+
+def assert_inverse(w, ref, levels, filt, cap, tag, ndim=2, do_swt=0):
+    """The inverse on its own: loads the reference bands into the plan `w` (set_coeff), inverts, and compares with inverse_reference at
+    its tolerance, `cap` * max(|image|, 1) at the most."""
+    for k, r in enumerate(ref):
+        w.set_coeff(r, k)
+    w.inverse()
+    got = np.asarray(w.image)
+    want, (tol, noise) = inverse_reference(ref, got.shape if got.ndim == 2 else (1, got.size), levels, filt, ndim=ndim, do_swt=do_swt)
+    err = float(np.abs(got.reshape(want.shape).astype(np.float64) - want).max())
+    assert err <= min(tol, cap * max(float(np.abs(want).max()), 1.0)), (tag, err, tol, noise)

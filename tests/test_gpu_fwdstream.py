@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
+import tap_banks
 
 pytestmark = pytest.mark.gpu
 
@@ -88,16 +89,14 @@ def test_fwdstream_batches_and_custom_banks():
         for b in range(B):
             for k, r in enumerate(oracle.forward(x[b], wname, L, do_swt=1)):
                 assert np.abs(bw.coeff_at(k, b) - r).max() <= 2e-6 * (1 + L) * max(float(np.abs(r).max()), 255.0), (wname, b, k)
-    rng = np.random.default_rng(7)
     for n, base in ((40, "db20"), (22, "db11"), (6, "db3")):
-        lo, hi, ilo, ihi = [rng.standard_normal(n).astype(np.float32) * 0.2 for _ in range(4)]
+        filt = tap_banks.bank(n, 7)  # every tap at least 0.5 / sqrt(n): none can go unseen (tests/tap_banks.py)
         x = oracle.hash_input((320, 512), 88 + n)
         w = Wavelets(x, base, 2, do_swt=1)
-        w.set_wavelets_filters("custom%d" % n, lo, hi, ilo, ihi)
+        w.set_wavelets_filters("custom%d" % n, *filt[1:])
         w.forward()
-        ref = oracle.forward(x, base, 2, do_swt=1, filt=(n, lo, hi, ilo, ihi))
-        for k, (g, r) in enumerate(zip(_flat(w.coeffs), ref)):
-            assert np.abs(g - r).max() <= 1e-5 * max(float(np.abs(r).max()), 1.0), (n, k)
+        # the fp32 oracle's own distance from its fp64-accumulating twin x tap_banks.K, 1e-5 of the band at the most
+        tap_banks.assert_forward(_flat(w.coeffs), x, 2, filt, 1e-5, n, do_swt=1)
 
 
 def test_fwdstream_nonfinite_footprint_matches_the_oracle():

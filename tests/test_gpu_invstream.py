@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
+import tap_banks
 
 pytestmark = pytest.mark.gpu
 
@@ -97,17 +98,16 @@ def test_invstream_batches_and_custom_banks():
             thr = oracle.threshold(oracle.forward(x[b], wname, L, do_swt=1), shape, L, "soft", 5.0, do_swt=1)
             want = oracle.inverse(thr, shape, wname, L, do_swt=1)
             assert np.abs(bw.image_at(b) - want).max() <= 4e-6 * (1 + L) * 255.0, (wname, b)
-    rng = np.random.default_rng(8)
     for n, base in ((20, "db10"), (14, "db7"), (6, "db3")):
-        lo, hi, ilo, ihi = [rng.standard_normal(n).astype(np.float32) * 0.2 for _ in range(4)]
+        filt = tap_banks.bank(n, 8)  # every tap at least 0.5 / sqrt(n): none can go unseen (tests/tap_banks.py)
         x = oracle.hash_input((320, 512), 98 + n)
         w = Wavelets(x, base, 2, do_swt=1)
-        w.set_wavelets_filters("custom%d" % n, lo, hi, ilo, ihi)
+        w.set_wavelets_filters("custom%d" % n, *filt[1:])
         w.forward()
-        ref = oracle.forward(x, base, 2, do_swt=1, filt=(n, lo, hi, ilo, ihi))
-        w.inverse()
-        want = oracle.inverse(ref, x.shape, base, 2, do_swt=1, filt=(n, lo, hi, ilo, ihi))
-        assert np.abs(w.image - want).max() <= 2e-5 * max(float(np.abs(want).max()), 1.0), n
+        ref, _ = tap_banks.forward_reference(x, 2, filt, do_swt=1)
+        # the inverse of the oracle's coefficients: the fp32 oracle's own distance from its fp64-accumulating twin x tap_banks.K,
+        # 2e-5 of the image at the most
+        tap_banks.assert_inverse(w, ref, 2, filt, 2e-5, n, do_swt=1)
 
 
 def test_invstream_nonfinite_footprint_matches_the_oracle():

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
+import tap_banks
 
 pytestmark = pytest.mark.gpu
 
@@ -109,20 +110,15 @@ def test_long_batched_plans_vs_oracle():
 def test_long_custom_filters():
     """Arbitrary 40-tap and 22-tap banks (set_wavelets_filters): nothing in the kernels depends on the taps being a wavelet's."""
     from pypwt_amd import Wavelets
-    rng = np.random.default_rng(6)
     for n, base in ((40, "db20"), (22, "db11")):
-        lo, hi, ilo, ihi = [rng.standard_normal(n).astype(np.float32) * 0.2 for _ in range(4)]
+        filt = tap_banks.bank(n, 6)  # every tap at least 0.5 / sqrt(n): none can go unseen (tests/tap_banks.py)
         x = oracle.hash_input((320, 512), 78 + n)
         w = Wavelets(x, base, 2)
-        w.set_wavelets_filters("custom%d" % n, lo, hi, ilo, ihi)
+        w.set_wavelets_filters("custom%d" % n, *filt[1:])
         w.forward()
-        filt = (n, lo, hi, ilo, ihi)
-        ref = oracle.forward(x, base, 2, filt=filt)
-        for k, (g, r) in enumerate(zip(_flat(w.coeffs), ref)):
-            assert np.abs(g - r).max() <= 1e-5 * max(float(np.abs(r).max()), 1.0), (n, k)
-        w.inverse()
-        want = oracle.inverse(ref, x.shape, base, 2, filt=filt)
-        assert np.abs(w.image - want).max() <= 1e-5 * max(float(np.abs(want).max()), 1.0), n
+        # the fp32 oracle's own distance from its fp64-accumulating twin x tap_banks.K, 1e-5 of the band at the most
+        ref = tap_banks.assert_forward(_flat(w.coeffs), x, 2, filt, 1e-5, n)
+        tap_banks.assert_inverse(w, ref, 2, filt, 1e-5, n)
 
 
 def test_long_nonfinite_footprint_matches_the_oracle():

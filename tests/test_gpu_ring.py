@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
+import tap_banks
 
 pytestmark = pytest.mark.gpu
 
@@ -79,19 +80,14 @@ def test_ring_batched_plans_vs_oracle():
 def test_ring_custom_filters_and_reconstruction():
     """Arbitrary 16-tap banks (set_wavelets_filters): nothing in the kernels depends on the taps being a wavelet's."""
     from pypwt_amd import Wavelets
-    rng = np.random.default_rng(5)
-    lo, hi, ilo, ihi = [rng.standard_normal(16).astype(np.float32) * 0.3 for _ in range(4)]
+    filt = tap_banks.bank(16, 5)  # every tap at least 0.5 / sqrt(n): none can go unseen (tests/tap_banks.py)
     x = oracle.hash_input((320, 512), 77)
     w = Wavelets(x, "sym8", 2)
-    w.set_wavelets_filters("custom16", lo, hi, ilo, ihi)
+    w.set_wavelets_filters("custom16", *filt[1:])
     w.forward()
-    filt = (16, lo, hi, ilo, ihi)
-    ref = oracle.forward(x, "sym8", 2, filt=filt)
-    for k, (g, r) in enumerate(zip(_flat(w.coeffs), ref)):
-        assert np.abs(g - r).max() <= 1e-5 * max(float(np.abs(r).max()), 1.0), k
-    w.inverse()
-    want = oracle.inverse(ref, x.shape, "sym8", 2, filt=filt)
-    assert np.abs(w.image - want).max() <= 1e-5 * max(float(np.abs(want).max()), 1.0)
+    # the fp32 oracle's own distance from its fp64-accumulating twin x tap_banks.K, 1e-5 of the band at the most
+    ref = tap_banks.assert_forward(_flat(w.coeffs), x, 2, filt, 1e-5, "ring")
+    tap_banks.assert_inverse(w, ref, 2, filt, 1e-5, "ring")
 
 
 def test_ring_full_size_every_element():

@@ -8,6 +8,7 @@ import pytest
 
 from golden_util import load_cases, ndim_of, rel_err, swt_of
 from oracle import oracle
+import tap_banks
 
 pytestmark = pytest.mark.gpu
 
@@ -108,18 +109,14 @@ def test_wave_kernels_batched_and_custom_filters():
     bw.inverse()
     assert np.abs(bw.image - x).max() < 7e-4
     # user-supplied separable bank of 8 taps (set_wavelets_filters, src/pypwt.pyx:487-575)
-    rng = np.random.default_rng(5)
-    lo, hi, ilo, ihi = [rng.standard_normal(8).astype(np.float32) for _ in range(4)]
+    filt = tap_banks.bank(8, 5)  # every tap at least 0.5 / sqrt(n): none can go unseen (tests/tap_banks.py)
     y = oracle.hash_input((64, 256), 8301, 10.0) - 5.0
     w = Wavelets(y, "db2", 2)
-    w.set_wavelets_filters("rand8", lo, hi, ilo, ihi)
+    w.set_wavelets_filters("rand8", *filt[1:])
     w.forward()
-    filt = (8, lo, hi, ilo, ihi)
-    ref = oracle.forward(y, "db4", 2, filt=filt)
-    for g, r in zip(_flat(w.coeffs), ref):
-        assert np.abs(g - r).max() <= 2e-5 * max(np.abs(r).max(), 1.0)
-    w.inverse()
-    assert np.abs(w.image - oracle.inverse(ref, y.shape, "db4", 2, filt=filt)).max() <= 2e-4 * max(np.abs(y).max(), 1.0) * 8
+    # the fp32 oracle's own distance from its fp64-accumulating twin x tap_banks.K, 2e-5 of the band at the most
+    ref = tap_banks.assert_forward(_flat(w.coeffs), y, 2, filt, 2e-5, "wave")
+    tap_banks.assert_inverse(w, ref, 2, filt, 2e-5, "wave")
 
 
 def test_wave_single_level_kernels_without_the_two_level_fusion():
