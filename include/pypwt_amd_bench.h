@@ -51,7 +51,8 @@ long long pdwt_copy_capacity(pdwt_handle h); /* the largest `elems` pdwt_time_co
  * kernel choice is fixed at compile time, pdwt/src/wt.cu:236-305).  Returns the previous value, or
  * PDWT_ERR_ARG for an unknown key.  Every key is read ONCE PER PLAN, when the plan is created (pdwt_create*, pdwt_clone
  * copies its source's): a plan keeps the values it was built with, so threads driving plans with different settings -- or a
- * thread that moves a knob -- cannot change another plan's kernel choice in mid-transform.  Keys:
+ * thread that moves a knob -- cannot change another plan's kernel choice in mid-transform.  Keys (the snapshot keys are
+ * the rows of pypwt_amd/csrc/tuning_knobs.inc, with their ranges and where their defaults come from):
  *   "wave_min_log2"  a 2D DWT level runs on the wave-per-tile kernels when at least 2^value samples
  *                    enter it (default 22, fp64 library 16; 0 = always when eligible; 63 = never)
  *   "lds_max_log2"   a 2D DWT level of at most 2^value samples prefers the LDS tiles to the wave-per-tile kernels

@@ -109,6 +109,14 @@ def _compile(job):
     return obj
 
 
+def _jobs_per_variant():
+    """Compiler processes of one variant: half the CPUs (build_all runs three variants at once).  A host that reports more CPUs than
+    a command may use says so in MAX_JOBS: the three variants together then stay within it (anything but a number is ignored)."""
+    half = max(2, (os.cpu_count() or 4) // 2)
+    limit = os.environ.get("MAX_JOBS", "")
+    return min(half, max(1, int(limit) // 3)) if limit.isdigit() else half
+
+
 def build_library(force=False, verbose=True, variant="f32"):
     objdir, lib, extra, skip = VARIANTS[variant]
     os.makedirs(objdir, exist_ok=True)
@@ -119,7 +127,7 @@ def build_library(force=False, verbose=True, variant="f32"):
         for f in os.listdir(objdir):
             if os.path.isfile(os.path.join(objdir, f)):  # (build/obj/cy is the Cython binding's directory)
                 os.remove(os.path.join(objdir, f))
-    with ThreadPoolExecutor(max_workers=min(max(2, (os.cpu_count() or 4) // 2), len(srcs))) as ex:
+    with ThreadPoolExecutor(max_workers=min(_jobs_per_variant(), len(srcs))) as ex:
         objs = list(ex.map(_compile, [(s, objdir, extra) for s in srcs]))
     cmd = [hipcc(), "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", lib] + objs
     r = subprocess.run(cmd, capture_output=True, text=True)

@@ -31,19 +31,26 @@ struct BandTable {
     int blk[kMaxBands + 1];
 };
 
-// Dispatch knobs that a level LAUNCH consults (pdwt_set_tuning).  A plan takes a snapshot when it is created and makes it
-// the calling thread's active set around its launches, so that two threads driving plans with different settings -- or a
-// third thread calling pdwt_set_tuning -- cannot change each other's kernel choice in mid-transform; with no active set
-// (direct calls of the launchers: tools, emulation) the process-wide values apply.
-struct Tuning {
-    int wave_min_log2, lds_max_log2, swt_split_fwd, swt_split_inv, dwt_split_fwd, dwt_split_inv, ring_min_log2, long_fwd, long_inv, swt_colstream, swt_fwdstream, swt_invstream;
-    int wave2, swt_fused, chain, reg1d;  // read by build_schedule: a clone rebuilds its launch lists from its source's values
+// Dispatch knobs that a process can move at run time (pdwt_set_tuning): the rows of tuning_knobs.inc.  A plan takes a snapshot
+// when it is created and makes it the calling thread's active set around its launches, so that two threads driving plans with
+// different settings -- or a third thread calling pdwt_set_tuning -- cannot change each other's kernel choice in mid-transform;
+// with no active set (direct calls of the launchers: tools, emulation) the process-wide values apply.
+enum class Knob : int {
+#define PDWT_KNOB(key, lo, hi, init, what) key,
+#include "tuning_knobs.inc"
+#undef PDWT_KNOB
 };
+struct Tuning {
+#define PDWT_KNOB(key, lo, hi, init, what) int key;
+#include "tuning_knobs.inc"
+#undef PDWT_KNOB
+};
+constexpr int kKnobCount = sizeof(Tuning) / sizeof(int);
+int knob(Knob k);                         // what every launcher reads: the active snapshot's value, else the process-wide one
+int set_knob(Knob k, int value);          // the process-wide value, clamped as the row says; returns the previous one
 Tuning current_tuning();                  // the process-wide values now
 void set_active_tuning(const Tuning* t);  // thread-local; nullptr = the process-wide values
 const Tuning* active_tuning();
-int get_swt_split_min(int inverse);
-int get_dwt_split_min(int inverse);
 struct ActiveTuning {  // RAII: the plan's snapshot for the duration of a forward / inverse
     const Tuning* prev;
     explicit ActiveTuning(const Tuning* t) : prev(active_tuning()) { set_active_tuning(t); }
@@ -71,26 +78,6 @@ hipError_t try_launch_dwt2_inv_ring(const Inv2DArgs& a, int batch, hipStream_t s
 // forces the rows per segment
 hipError_t try_launch_dwt2_fwd_long(const Fwd2DArgs& a, int batch, hipStream_t s, int seg_hint = 0);
 hipError_t try_launch_dwt2_inv_long(const Inv2DArgs& a, int batch, hipStream_t s, int seg_hint = 0);
-int set_long_min_taps(int inverse, int taps);  // shortest filter on them (0: never; 100 + n: n taps at every size they take); returns the previous value
-int get_long_min_taps(int inverse);
-int set_swt_colstream_min(int taps);  // column pass of the two-launch SWT levels streamed through an LDS history (swt_colstream_kernels.hpp) from `taps` taps; 0: never
-int get_swt_colstream_min();
-int set_swt_fwdstream_min(int taps);  // forward SWT levels in one launch (swt_fwdstream_kernels.hpp) from `taps` taps; 0: never; 100 + n: n taps at every size
-int get_swt_fwdstream_min();
-int set_swt_invstream_min(int taps);  // ... inverse SWT levels in one launch (swt_invstream_kernels.hpp)
-int get_swt_invstream_min();
-int set_ring_min_log2(int value);  // 2D DWT levels of at least 2^value samples with 12-20 taps run on them (63 = never; below the default: 10-20 taps, tests)
-int get_ring_min_log2();
-int set_wave_min_log2(int value);  // returns the previous threshold
-int get_wave_min_log2();
-int set_lds_max_log2(int value);   // 2D DWT levels of at most 2^value samples prefer the LDS tiles to the wave kernels (0 = never)
-int get_lds_max_log2();
-int set_wave2_enabled(int value);  // two-levels-per-wavefront forward (opt-in); returns the previous setting
-int get_wave2_enabled();
-int set_swt_fused_enabled(int value);  // 2-tap 2D SWT levels 1-3 / 4-6 in one launch each (swt2_fused_kernels.hpp); read when a plan is built
-int get_swt_fused_enabled();
-int set_reg1d_enabled(int value);   // 1D levels three at a time in registers (dwt1_reg_kernels.hpp); bit 0 forward, bit 1 inverse; read when a plan is built
-int get_reg1d_enabled();
 // two forward levels per wavefront (A_l stays in registers); contract of launch_dwt2_fwd_pyr2
 bool dwt2_wave2_supported(int hlen, int N0r, int N0c);
 hipError_t launch_dwt2_fwd_wave2(const real_t* in, real_t* const det1[3], real_t* const band2[4], int N0r, int N0c,
@@ -117,8 +104,6 @@ hipError_t launch_dwt2_fwd_chain(const real_t* in, real_t* const* det, real_t* c
                                  const FilterBank& fb, int batch, unsigned* flags, unsigned epoch, hipStream_t s);
 hipError_t launch_dwt2_inv_chain(real_t* out, real_t* const* det, real_t* const* app, int Nr, int Nc, int K, int hlen,
                                  const FilterBank& fb, int batch, unsigned* flags, unsigned epoch, hipStream_t s);
-int set_chain_enabled(int value);  // 0 never (the default: opt-in, and the product build stubs the chain kernels out), 1 one cache-resident image + batch inverses, 2 wherever supported (tests), 3 = 2 + batch forwards too
-int get_chain_enabled();
 int set_chain_timeout(int ticks);  // s_memrealtime ticks (100 MHz) a chained tile waits for a producer before computing it itself
 // three consecutive 2D levels in one launch, small images (launch_dwt2_pyr3.hip): det[3 k + b] = band b (H, V, D) of the
 // k-th level of the group (finest first); rows and columns multiples of 8, even filters of at most 16 taps (fp64: 8)
@@ -166,12 +151,10 @@ bool swt2_inv_stream_takes(const Swt2DArgs& a, int batch);
 hipError_t try_launch_swt2_inv_stream(const Swt2DArgs& a, int batch, hipStream_t s);
 // one a-trous level as a row launch + a column launch through scratch (2 Nr Nc batch elements): swt_split_kernels.hpp
 bool swt2_split_supported(int hlen, int Nr, int Nc, int f, bool inverse, long long samples_per_launch);
-int set_swt_split_min(int inverse, int taps);  // shortest filter on the split path (0: never); returns the previous value
 hipError_t launch_swt2_split(const Swt2DArgs& a, real_t* scratch, bool inverse, int batch, hipStream_t s);
 // one DECIMATED 2D level as a row launch + a column launch through scratch (Nr Nc batch elements): dwt2_split_kernels.hpp;
 // (Nr, Nc) = the level's image side (forward: its input, inverse: its output), both even, Nc a multiple of 8
 bool dwt2_split_supported(int hlen, int Nr, int Nc, bool inverse, long long samples_per_launch);
-int set_dwt_split_min(int inverse, int taps);  // shortest filter on the split path (0: never; 100 + n: n taps at every size); returns the previous value
 hipError_t launch_dwt2_split_fwd(const Fwd2DArgs& a, real_t* scratch, int batch, hipStream_t s);
 hipError_t launch_dwt2_split_inv(const Inv2DArgs& a, real_t* scratch, int batch, hipStream_t s);
 // levels l0 .. l0+K-1 (K = 2, 3; l0 = 1 or 4) of a 2-tap 2D SWT in one launch (swt2_fused_kernels.hpp)

@@ -1,4 +1,5 @@
 // launch_dwt2.hip -- instantiations + launchers of the fused 2D DWT level kernels (gfx950).
+#include <limits.h>
 #include <stdlib.h>
 
 #include <atomic>
@@ -85,45 +86,9 @@ hipError_t launch_dwt2_inv_chain(real_t*, real_t* const*, real_t* const*, int, i
 // (numbers in launch_dwt2_wave.hip).  PDWT_NO_WAVE=1 (read once) keeps the LDS tiles everywhere, PDWT_WAVE_MIN /
 // pdwt_set_tuning("wave_min_log2") override the threshold (log2 samples): tests and A/B measurements.
 // fp64 build: the alternative is the generic kernel, not a tuned LDS tile, so the wave kernels start at 2^16 samples
-#ifdef PDWT_DOUBLE
-constexpr int kWaveMinDefault = (int)tune::wave_min_log2_f64;
-#else
-constexpr int kWaveMinDefault = (int)tune::wave_min_log2;
-#endif
-static std::atomic<int>& wave_min_log2() {
-    static std::atomic<int> v{lab_env("PDWT_NO_WAVE") ? 63 : (lab_env("PDWT_WAVE_MIN") ? atoi(lab_env("PDWT_WAVE_MIN")) : kWaveMinDefault)};
-    return v;
-}
-int set_wave_min_log2(int value) {  // pdwt_set_tuning("wave_min_log2")
-    if (value < 0) value = 0;
-    if (value > 63) value = 63;
-    return wave_min_log2().exchange(value);
-}
-int get_wave_min_log2() { return wave_min_log2().load(std::memory_order_relaxed); }
-static std::atomic<int>& wave2_flag() {
-    static std::atomic<int> v{lab_env("PDWT_WAVE2") ? 1 : 0};
-    return v;
-}
-static std::atomic<int>& swt_fused_flag() {
-    static std::atomic<int> v{lab_env("PDWT_SWT_FUSED") ? atoi(lab_env("PDWT_SWT_FUSED")) : 1};
-    return v;
-}
-int set_swt_fused_enabled(int value) { return swt_fused_flag().exchange(value < 0 ? 0 : (value > 2 ? 2 : value)); }
-int get_swt_fused_enabled() { return swt_fused_flag().load(std::memory_order_relaxed); }
-static std::atomic<int>& reg1d_flag() {
-    static std::atomic<int> v{lab_env("PDWT_REG1D") ? (atoi(lab_env("PDWT_REG1D")) & 15) : 3};
-    return v;
-}
-int set_reg1d_enabled(int value) { return reg1d_flag().exchange(value < 0 ? 0 : (value > 15 ? 15 : value)); }  // four flag bits
-int get_reg1d_enabled() { return reg1d_flag().load(std::memory_order_relaxed); }
-static std::atomic<int>& chain_flag() {
-    static std::atomic<int> v{lab_env("PDWT_CHAIN") ? atoi(lab_env("PDWT_CHAIN")) : 0};  // opt-in: measured no faster, see plan.cpp
-    return v;
-}
-int set_chain_enabled(int value) { return chain_flag().exchange(value < 0 ? 0 : (value > 3 ? 3 : value)); }
-int get_chain_enabled() { return chain_flag().load(std::memory_order_relaxed); }
-int set_wave2_enabled(int value) { return wave2_flag().exchange(value ? 1 : 0); }
-int get_wave2_enabled() { return wave2_flag().load(std::memory_order_relaxed); }
+// (the predicates below compare against the same default that the wave_min_log2 row of tuning_knobs.inc starts from; PDWT_BY_BUILD is
+// the fp32 / fp64 selector that file defines and leaves defined, it arrives here with launch.hpp)
+constexpr int kWaveMinDefault = PDWT_BY_BUILD((int)tune::wave_min_log2, (int)tune::wave_min_log2_f64);
 static thread_local const char* g_last_family = "";
 void note_family(const char* family) { g_last_family = family; }
 const char* last_family() { return g_last_family; }
@@ -133,9 +98,44 @@ static bool took(hipError_t e, const char* family) {
     note_family(family);
     return true;
 }
+
+// ---- the run-time knobs (tuning_knobs.inc): process-wide store, per-plan snapshot, the one accessor of the launchers
+constexpr int kNoLimit = INT_MAX;
+static std::atomic<int>* knob_store() {  // first use of any knob: the lab library reads its environment here
+    static std::atomic<int> v[kKnobCount] = {
+#define PDWT_KNOB(key, lo, hi, init, what) {init},
+#include "tuning_knobs.inc"
+#undef PDWT_KNOB
+    };
+    return v;
+}
+static constexpr int Tuning::*kKnobField[kKnobCount] = {
+#define PDWT_KNOB(key, lo, hi, init, what) &Tuning::key,
+#include "tuning_knobs.inc"
+#undef PDWT_KNOB
+};
 static thread_local const Tuning* g_active_tuning = nullptr;
 void set_active_tuning(const Tuning* t) { g_active_tuning = t; }
 const Tuning* active_tuning() { return g_active_tuning; }
+int knob(Knob k) {
+    const Tuning* t = g_active_tuning;
+    return t ? t->*kKnobField[(int)k] : knob_store()[(int)k].load(std::memory_order_relaxed);
+}
+int set_knob(Knob k, int value) {  // pdwt_set_tuning: 0 as it is, anything else clamped to the row's [lo, hi]
+    static constexpr int range[kKnobCount][2] = {
+#define PDWT_KNOB(key, lo, hi, init, what) {lo, hi},
+#include "tuning_knobs.inc"
+#undef PDWT_KNOB
+    };
+    const int lo = range[(int)k][0], hi = range[(int)k][1];
+    return knob_store()[(int)k].exchange(value == 0 ? 0 : (value < lo ? lo : (value > hi ? hi : value)));
+}
+Tuning current_tuning() {
+    Tuning t;
+    for (int k = 0; k < kKnobCount; ++k) t.*kKnobField[k] = knob_store()[k].load(std::memory_order_relaxed);
+    return t;
+}
+
 // Register-ring kernels (dwt2_ring_kernels.hpp): 38 % fewer vector instructions than the LDS tile at 16 taps (rocprofv3
 // SQ_INSTS_VALU per 4096^2 level: 11.1e6 -> 6.9e6, profiles/r05a_*), but a level is only as fast as its wavefronts are many:
 // same-box A/B inside plans (tools/ring_ab.py, profiles/r05c_ring_ab.txt; forward + inverse of the whole plan, tiles -> ring):
@@ -147,14 +147,8 @@ const Tuning* active_tuning() { return g_active_tuning; }
 // Default: levels of at least 2^25 samples, 12 or 16 taps, rows of at least 1024 columns.  Tuning key "ring_min_log2"
 // (63 = never; below the default: every level of 10-20 taps and any width of that size on -- tests and measurements).
 constexpr int kRingMinDefault = (int)tune::ring_min_log2;
-static std::atomic<int>& ring_min_log2() {
-    static std::atomic<int> v{kRingMinDefault};
-    return v;
-}
-int set_ring_min_log2(int value) { return ring_min_log2().exchange(value < 0 ? 0 : (value > 63 ? 63 : value)); }
-int get_ring_min_log2() { return ring_min_log2().load(std::memory_order_relaxed); }
 static bool ring_kernels_for(long long samples, int hlen, int Nc, bool inverse) {
-    const int m = g_active_tuning ? g_active_tuning->ring_min_log2 : ring_min_log2().load(std::memory_order_relaxed);
+    const int m = knob(Knob::ring_min_log2);
     if (m >= 63 || samples < (1LL << m)) return false;
     static const int dirs = lab_env("PDWT_RING_DIRS") ? atoi(lab_env("PDWT_RING_DIRS")) : 3;  // A/B measurements: bit 0 forward, bit 1 inverse
     if (!((dirs >> (inverse ? 1 : 0)) & 1)) return false;
@@ -175,18 +169,11 @@ static bool ring_kernels_for(long long samples, int hlen, int Nc, bool inverse) 
 //     db9   (18 taps)     43 /  47 ->  45 /  49 (forced)        172 / 193 -> 159 / 176
 //     db14  4096^2        61 /  76 ->  56 /  57;  db15  62 / 68 -> 55 / 59;  db13 forward 51 -> 53: the forward of one image from 28 taps
 //     db20  2048^2 L5     38 /  45 ->  53 /  56 with every level forced; level 1 of the inverse alone: 45 -> 40 (db16 38 -> 35, db15 31 -> 32)
-// Rules (tuning keys "long_fwd" / "long_inv": the shortest filter, default 18; 0 = never; 100 + n = n taps at every size the
+// Rules (tuning keys "long_fwd" / "long_inv": the shortest filter, default tune::long_min_taps = 18; 0 = never; 100 + n = n taps at every size the
 // kernels take: tests): 18 taps from 2^26 samples per launch; 20 taps and more: the inverse from 2^24 samples, the forward
 // from 2^25; the forward of 28 taps and more from 2^24; the inverse of 32 taps and more from 2^22.
-constexpr int kLongFwdDefault = (int)tune::long_min_taps, kLongInvDefault = (int)tune::long_min_taps;
-static std::atomic<int>& long_min_taps(bool inverse) {
-    static std::atomic<int> v[2] = {{kLongFwdDefault}, {kLongInvDefault}};
-    return v[inverse ? 1 : 0];
-}
-int set_long_min_taps(int inverse, int taps) { return long_min_taps(inverse != 0).exchange(taps < 0 ? 0 : taps); }
-int get_long_min_taps(int inverse) { return long_min_taps(inverse != 0).load(std::memory_order_relaxed); }
 static bool long_kernels_for(long long samples, int hlen, bool inverse) {
-    const int m = g_active_tuning ? (inverse ? g_active_tuning->long_inv : g_active_tuning->long_fwd) : get_long_min_taps(inverse);
+    const int m = knob(inverse ? Knob::long_inv : Knob::long_fwd);
     if (m <= 0) return false;
     if (m >= 100) return hlen >= m - 100;  // forced: every size
     if (hlen < m) return false;
@@ -202,9 +189,8 @@ static bool long_kernels_for(long long samples, int hlen, bool inverse) {
     return hlen >= tune::long_fwd_mid_taps && samples >= (1LL << tune::long_fwd_mid_log2);
 }
 
-static int eff_wave_min_log2() { return g_active_tuning ? g_active_tuning->wave_min_log2 : wave_min_log2().load(std::memory_order_relaxed); }
 static bool wave_kernels_for(long long samples) {
-    const int m = eff_wave_min_log2();
+    const int m = knob(Knob::wave_min_log2);
     return m < 63 && samples >= (1LL << m);
 }
 
@@ -218,21 +204,11 @@ static bool wave_kernels_for(long long samples) {
 // directions (forward+inverse db4 2 x 4096^2 173 -> 170 us, 8 x 2048^2 170 -> 161, 32 x 1024^2 165 -> 152; haar 2 x 4096^2
 // 151 -> 139): the default limit is 25.  Above, the wave INVERSE stays ahead (3-8 %), and the wave FORWARD only on images of
 // 2^24 samples (3 x 4096^2: 110 against 117 us; 12 x 2048^2: 114 against 101, 48 x 1024^2: 116 against 97 on the tiles).
-#ifdef PDWT_DOUBLE
-constexpr int kLdsMaxDefault = 0;   // no tuned LDS tiles in the fp64 build
-#else
-constexpr int kLdsMaxDefault = (int)tune::lds_max_log2;
-#endif
-static std::atomic<int>& lds_max_log2() {
-    static std::atomic<int> v{lab_env("PDWT_LDS_MAX") ? atoi(lab_env("PDWT_LDS_MAX")) : kLdsMaxDefault};
-    return v;
-}
-int set_lds_max_log2(int value) { return lds_max_log2().exchange(value < 0 ? 0 : (value > 62 ? 62 : value)); }
-int get_lds_max_log2() { return lds_max_log2().load(std::memory_order_relaxed); }
+constexpr int kLdsMaxDefault = PDWT_BY_BUILD((int)tune::lds_max_log2, 0);  // = the lds_max_log2 row of tuning_knobs.inc; no tuned LDS tiles in the fp64 build
 static bool lds_tiles_for(long long samples, int hlen, long long per_image = 0, bool inverse = true) {
     // ... and only above 2^22 samples: in the step the 2048^2 level of cfg2 is 0.3-0.4 us faster on the wave kernels
     // (10.6 / 11.6 against 11.0 / 11.9 us event-timed), the 4096^2 level 1.0 / 0.3 us faster on the tiles
-    const int m = g_active_tuning ? g_active_tuning->lds_max_log2 : lds_max_log2().load(std::memory_order_relaxed);
+    const int m = knob(Knob::lds_max_log2);
     if (m <= 0 || (hlen & 1) || samples <= (1LL << tune::lds_tiles_above_log2)) return false;
     if (samples <= (1LL << m)) return true;
     // forward levels of smaller images, up to where the strips take over
@@ -246,28 +222,7 @@ static bool lds_tiles_for(long long samples, int hlen, long long per_image = 0, 
 // no tuned tile to fall back to); a threshold forced below its default -- tests -- still takes the wave kernels.
 static bool narrow_for_wave(int Nc) {
     static const int min_nc = lab_env("PDWT_WAVE_MIN_NC") ? atoi(lab_env("PDWT_WAVE_MIN_NC")) : (int)tune::wave_min_columns;  // two full strips; A/B measurements
-    return sizeof(real_t) == 4 && Nc < min_nc && eff_wave_min_log2() >= kWaveMinDefault;
-}
-
-Tuning current_tuning() {
-    Tuning t;
-    t.wave_min_log2 = get_wave_min_log2();
-    t.lds_max_log2 = get_lds_max_log2();
-    t.swt_split_fwd = get_swt_split_min(0);
-    t.swt_split_inv = get_swt_split_min(1);
-    t.dwt_split_fwd = get_dwt_split_min(0);
-    t.dwt_split_inv = get_dwt_split_min(1);
-    t.ring_min_log2 = get_ring_min_log2();
-    t.long_fwd = get_long_min_taps(0);
-    t.long_inv = get_long_min_taps(1);
-    t.swt_colstream = get_swt_colstream_min();
-    t.swt_fwdstream = get_swt_fwdstream_min();
-    t.swt_invstream = get_swt_invstream_min();
-    t.wave2 = get_wave2_enabled();
-    t.swt_fused = get_swt_fused_enabled();
-    t.chain = get_chain_enabled();
-    t.reg1d = get_reg1d_enabled();
-    return t;
+    return sizeof(real_t) == 4 && Nc < min_nc && knob(Knob::wave_min_log2) >= kWaveMinDefault;
 }
 
 hipError_t launch_dwt2_fwd(const Fwd2DArgs& a, int batch, hipStream_t s) {
@@ -287,7 +242,7 @@ hipError_t launch_dwt2_fwd(const Fwd2DArgs& a, int batch, hipStream_t s) {
     // store round trip per four rows -- db2 2048^2 22.6 us against 9.8 us on the LDS tiles, found in round 4 by the reference's
     // own benchmark plan dwt2 db2 2048^2 L9: 44.7 us; the other lengths are level with the tiles there)
     // (a threshold forced below its default -- tests -- still takes it)
-    const bool slow4 = sizeof(real_t) == 4 && a.hlen == 4 && eff_wave_min_log2() >= kWaveMinDefault;
+    const bool slow4 = sizeof(real_t) == 4 && a.hlen == 4 && knob(Knob::wave_min_log2) >= kWaveMinDefault;
     if (wave_kernels_for((long long)batch * a.Nr * a.Nc) && !slow4 && !narrow_for_wave(a.Nc)) {
         const hipError_t e = try_launch_dwt2_fwd_wave(a, batch, s);
         if (took(e, "wave")) return e;

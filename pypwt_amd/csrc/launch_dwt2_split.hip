@@ -12,7 +12,6 @@
 // of a 2048^2 level of 40 taps, wavefronts resident ~60 % of the time, VALU 25 % busy), and every small level pays two
 // launch latencies (2 x 5-6 us) where one tile launch now takes 5-6.  Kept with its emulation and GPU parity tests
 // (tests/test_emu_tiles.py::test_emu_dwt_split_*, tests/test_gpu_parity.py::test_dwt_two_launch_levels).
-#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 
@@ -27,25 +26,11 @@
 
 namespace pdwt {
 
-static int env_int_d(const char* name, int dflt) {
-    const char* e = lab_env(name);
-    return e ? atoi(e) : dflt;
-}
-
 // Shortest (even) filter whose decimated 2D levels run as a row launch + a column launch through scratch instead of one
 // LDS-tiled launch.  Tuning keys "dwt_split_fwd" / "dwt_split_inv" (environment PDWT_DWT_SPLIT_FWD / _INV): 0 = never
-// (default), 100 + n = n taps at EVERY size (tests).  The product keeps the value and does nothing with it.
-#ifdef PDWT_DOUBLE
-constexpr int kDsplitDefault = 28;  // fp64 library: the any-length stream kernels (dwt2_stream_kernels.hpp), see below
-#else
-constexpr int kDsplitDefault = 0;
-#endif
-static std::atomic<int>& dsplit_min(bool inverse) {
-    static std::atomic<int> fwd{env_int_d("PDWT_DWT_SPLIT_FWD", kDsplitDefault)}, inv{env_int_d("PDWT_DWT_SPLIT_INV", kDsplitDefault)};
-    return inverse ? inv : fwd;
-}
-int set_dwt_split_min(int inverse, int taps) { return dsplit_min(inverse != 0).exchange(taps < 0 ? 0 : taps); }
-int get_dwt_split_min(int inverse) { return dsplit_min(inverse != 0).load(std::memory_order_relaxed); }
+// (default), 100 + n = n taps at EVERY size (tests).  The product keeps the value and does nothing with it.  The fp64 library
+// (default 28) runs such levels on the any-length stream kernels (dwt2_stream_kernels.hpp), see below.
+static int dsplit_min(bool inverse) { return knob(inverse ? Knob::dwt_split_inv : Knob::dwt_split_fwd); }
 
 #if defined(PDWT_DOUBLE)
 // ---- fp64 library (round 5): a row launch + a column launch of the any-length stream kernels.  Over doubles the LDS tiles of a
@@ -56,8 +41,7 @@ int get_dwt_split_min(int inverse) { return dsplit_min(inverse != 0).load(std::m
 // 64-B lane stride).  Tuning keys as in the fp32 lab library: 0 = never, n = from n taps where the rule below allows, 100 + n = n taps
 // at every size and in both directions' own key (tests).
 bool dwt2_split_supported(int hlen, int Nr, int Nc, bool inverse, long long samples) {
-    const Tuning* at = active_tuning();
-    int min_taps = at ? (inverse ? at->dwt_split_inv : at->dwt_split_fwd) : dsplit_min(inverse).load(std::memory_order_relaxed);
+    int min_taps = dsplit_min(inverse);
     if (min_taps <= 0) return false;
     if (min_taps >= 100) {
         min_taps -= 100;
@@ -164,8 +148,7 @@ static inline v2f mk2d(real_t a, real_t b) {
 
 // (Nr, Nc): the level's image side (forward: its input, inverse: its output); samples: over the whole batch
 bool dwt2_split_supported(int hlen, int Nr, int Nc, bool inverse, long long samples) {
-    const Tuning* at = active_tuning();
-    int min_taps = at ? (inverse ? at->dwt_split_inv : at->dwt_split_fwd) : dsplit_min(inverse).load(std::memory_order_relaxed);
+    int min_taps = dsplit_min(inverse);
     if (min_taps <= 0) return false;
     if (min_taps >= 100) {
         min_taps -= 100;  // forced: the same threshold at every size (tests)

@@ -12,14 +12,6 @@
 
 namespace pdwt {
 
-// shortest filter on these kernels (tuning key "swt_fwdstream"; 0 = never, 100 + n = n taps at every size they take)
-static std::atomic<int>& fwdstream_min() {
-    static std::atomic<int> v{(int)tune::swt_fwdstream_taps};
-    return v;
-}
-int set_swt_fwdstream_min(int taps) { return fwdstream_min().exchange(taps < 0 ? 0 : taps); }
-int get_swt_fwdstream_min() { return fwdstream_min().load(std::memory_order_relaxed); }
-
 // The fp64 library (the reference's DOUBLEPRECISION build, pdwt/src/filters.h:16-30) runs the same kernels for 6-20 taps at dilations 1-8:
 // steps of 16 rows (an element is 8 bytes: 36 KB of history + 11-20 KB of staged rows at 20 taps), the 40 tap registers of fp32's 40 taps
 constexpr bool kF64 = sizeof(real_t) == 8;
@@ -73,8 +65,8 @@ static hipError_t run(const Swt2DArgs& g, int batch, hipStream_t s) {
 #endif
 
 bool swt2_fwd_stream_takes(const Swt2DArgs& a, int batch) {
-    const Tuning* at = active_tuning();
-    int min_taps = at ? at->swt_fwdstream : get_swt_fwdstream_min();
+    // shortest filter on these kernels: tuning key "swt_fwdstream" (default tune::swt_fwdstream_taps; 0 = never, 100 + n = n taps at every size they take)
+    int min_taps = knob(Knob::swt_fwdstream);
     const bool forced = min_taps >= 100;
     if (forced) min_taps -= 100;
     if (min_taps <= 0 || a.hlen < min_taps || a.hlen < 6 || (a.hlen & 1) || a.hlen > kFwdStreamMaxTaps) return false;

@@ -12,14 +12,6 @@
 
 namespace pdwt {
 
-// shortest filter on these kernels (tuning key "swt_invstream"; 0 = never, 100 + n = n taps at every size they take)
-static std::atomic<int>& invstream_min() {
-    static std::atomic<int> v{(int)tune::swt_invstream_taps};
-    return v;
-}
-int set_swt_invstream_min(int taps) { return invstream_min().exchange(taps < 0 ? 0 : taps); }
-int get_swt_invstream_min() { return invstream_min().load(std::memory_order_relaxed); }
-
 // The fp64 library runs the same kernels for 6-16 taps at dilations 1-4, in steps of 16 rows (launch_swt_fwdstream.hip)
 constexpr bool kF64 = sizeof(real_t) == 8;
 constexpr int kInvStreamMaxTaps = kF64 ? 16 : 28, kInvStreamMaxF = kF64 ? 4 : 8;
@@ -73,8 +65,8 @@ static hipError_t run(const Swt2DArgs& g, int batch, hipStream_t s) {
 #endif
 
 bool swt2_inv_stream_takes(const Swt2DArgs& a, int batch) {
-    const Tuning* at = active_tuning();
-    int min_taps = at ? at->swt_invstream : get_swt_invstream_min();
+    // shortest filter on these kernels: tuning key "swt_invstream" (default tune::swt_invstream_taps; 0 = never, 100 + n = n taps at every size they take)
+    int min_taps = knob(Knob::swt_invstream);
     const bool forced = min_taps >= 100;
     if (forced) min_taps -= 100;
     if (min_taps <= 0 || a.hlen < min_taps || a.hlen < 6 || (a.hlen & 1) || a.hlen > kMaxTaps) return false;

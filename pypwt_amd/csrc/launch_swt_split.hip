@@ -20,14 +20,6 @@ static int env_int(const char* name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
-// shortest filter whose column pass runs on the strip kernels of swt_colstream_kernels.hpp (fp32 library; tuning key "swt_colstream")
-static std::atomic<int>& colstream_min() {
-    static std::atomic<int> v{(int)tune::swt_colstream_taps};
-    return v;
-}
-int set_swt_colstream_min(int taps) { return colstream_min().exchange(taps < 0 ? 0 : taps); }
-int get_swt_colstream_min() { return colstream_min().load(std::memory_order_relaxed); }
-
 // ---- the any-length stream kernels (swt_stream_kernels.hpp, round 5): both libraries ----------------------------------------------
 static void stream_taps(SwtStreamArgs& k, const FilterBank& fb, int hlen) {
     for (int j = 0; j < kStreamTaps; ++j) k.tl[j] = k.th[j] = 0;
@@ -122,19 +114,13 @@ static hipError_t stream_pass1d(const SwtPassArgs& a, bool inverse, hipStream_t 
     return inverse ? run_stream<true, false>(k, pairs, s) : run_stream<false, false>(k, pairs, s);
 }
 
+// shortest filter on the two-launch path: tuning keys "swt_split_fwd" / "swt_split_inv" (0 = never, 100 + n = n taps at every size)
+static int split_min(bool inverse) { return knob(inverse ? Knob::swt_split_inv : Knob::swt_split_fwd); }
+
 #ifdef PDWT_DOUBLE
 // ---- fp64 library: the two launches are ALWAYS the stream kernels ------------------------------------------------------------------
-// shortest filter on this path (tuning keys "swt_split_fwd" / "swt_split_inv"; 0 = never, 100 + n = n taps at every size)
-static std::atomic<int>& split_min(bool inverse) {
-    static std::atomic<int> fwd{env_int("PDWT_SWT_SPLIT_FWD", 12)}, inv{env_int("PDWT_SWT_SPLIT_INV", 6)};
-    return inverse ? inv : fwd;
-}
-int set_swt_split_min(int inverse, int taps) { return split_min(inverse != 0).exchange(taps < 0 ? 0 : taps); }
-int get_swt_split_min(int inverse) { return split_min(inverse != 0).load(std::memory_order_relaxed); }
-
 bool swt2_split_supported(int hlen, int Nr, int Nc, int f, bool inverse, long long samples) {
-    const Tuning* at = active_tuning();
-    int min_taps = at ? (inverse ? at->swt_split_inv : at->swt_split_fwd) : split_min(inverse).load(std::memory_order_relaxed);
+    int min_taps = split_min(inverse);
     if (min_taps <= 0) return false;
     if (min_taps >= 100) min_taps -= 100;
     (void)samples;
@@ -150,8 +136,7 @@ hipError_t launch_swt2_split(const Swt2DArgs& a, real_t* tmp, bool inverse, int 
 }
 
 hipError_t try_launch_swt1_split(const SwtPassArgs& a, bool inverse, hipStream_t s) {
-    const Tuning* at = active_tuning();  // the same thresholds as the 2D level
-    int min_taps = at ? (inverse ? at->swt_split_inv : at->swt_split_fwd) : split_min(inverse).load(std::memory_order_relaxed);
+    int min_taps = split_min(inverse);  // the same thresholds as the 2D level
     if (min_taps >= 100) min_taps -= 100;
     if (min_taps <= 0 || a.hlen < min_taps) return hipErrorNotSupported;
     return stream_pass1d(a, inverse, s);
@@ -176,13 +161,8 @@ static inline v2f mk2h(real_t a, real_t b) {
 // on the two launches win from 14 taps -- sym8 2048^2 L3 forward 160 -> 102 us, L5 262 -> 173, 4096^2 L2 397 -> 320, 1080 x 1920 L3
 // 94 -> 80; db7 2048^2 L3 145 -> 100 -- at 1024^2 they lose (54 -> 61) and 12 taps are level (2048^2 107 -> 99, 4096^2 291 -> 300):
 // the default is 14 taps from 2^21 samples, 18 below.  Tuning keys "swt_split_fwd" / "swt_split_inv" (environment
-// PDWT_SWT_SPLIT_FWD / _INV): the shortest filter that takes this path at full size, 0 = never, 100 + n = n taps at EVERY size.
-static std::atomic<int>& split_min(bool inverse) {
-    static std::atomic<int> fwd{env_int("PDWT_SWT_SPLIT_FWD", (int)tune::swt_split_fwd_big_taps)}, inv{env_int("PDWT_SWT_SPLIT_INV", (int)tune::swt_split_inv_taps)};
-    return inverse ? inv : fwd;
-}
-int set_swt_split_min(int inverse, int taps) { return split_min(inverse != 0).exchange(taps < 0 ? 0 : taps); }
-int get_swt_split_min(int inverse) { return split_min(inverse != 0).load(std::memory_order_relaxed); }
+// PDWT_SWT_SPLIT_FWD / _INV; defaults tune::swt_split_fwd_big_taps / tune::swt_split_inv_taps): the shortest filter that takes
+// this path at full size, 0 = never, 100 + n = n taps at EVERY size.
 
 // Where the any-length stream kernels (swt_stream_kernels.hpp: one or two columns per work item, plain FMAs) serve the fp32 library
 // (round 5; tools/swt_stream32_ab.py, profiles/r05g_swt_stream32_*.txt, three levels forward | inverse, same box).
@@ -211,8 +191,7 @@ static bool stream_route32(int hlen, int Nr, int Nc, int f, bool inverse, long l
 }
 
 bool swt2_split_supported(int hlen, int Nr, int Nc, int f, bool inverse, long long samples) {
-    const Tuning* at = active_tuning();  // the calling plan's snapshot, else the process-wide value
-    int min_taps = at ? (inverse ? at->swt_split_inv : at->swt_split_fwd) : split_min(inverse).load(std::memory_order_relaxed);
+    int min_taps = split_min(inverse);
     if (min_taps <= 0) return false;
     if (stream_route32(hlen, Nr, Nc, f, inverse, samples, min_taps)) return true;
     // (narrow images keep this path too: measured, the tiled inverse is slower still there -- 4096 images of 64^2, db4 L2
@@ -255,9 +234,8 @@ static hipError_t run_colstream(const SwtSplitArgs& c, hipStream_t s) {
     } else {
         // Rules (tools/swt_colstream_ab.py, profiles/r06_swt_colstream.txt): the inverse gains at every size and dilation (2048^2: 7-25 %,
         // 4096^2: 25-45 %); the forward only where the register kernels' shared rows fall out of L1 / L2 -- from 2^23 samples per launch
-        // (4096^2: 7-36 %; 2048^2: +-5 %).  Tuning key "swt_colstream": shortest filter, 0 = never, 100 + n = n taps, both directions, every size.
-        const Tuning* at = active_tuning();
-        int min_taps = at ? at->swt_colstream : get_swt_colstream_min();
+        // (4096^2: 7-36 %; 2048^2: +-5 %).  Tuning key "swt_colstream": shortest filter (default tune::swt_colstream_taps), 0 = never, 100 + n = n taps, both directions, every size.
+        int min_taps = knob(Knob::swt_colstream);
         const bool forced = min_taps >= 100;
         if (forced) min_taps -= 100;
         if (min_taps <= 0 || HLEN < min_taps) return hipErrorNotSupported;
@@ -403,13 +381,9 @@ hipError_t try_launch_swt1_split(const SwtPassArgs& a, bool inverse, hipStream_t
 // scratch: 2 * Nr * Nc * batch elements, 16-B aligned
 hipError_t launch_swt2_split(const Swt2DArgs& a, real_t* tmp, bool inverse, int batch, hipStream_t s) {
     if (!swt2_split_supported(a.hlen, a.Nr, a.Nc, a.f, inverse, (long long)batch * a.Nr * a.Nc) || !tmp) return hipErrorNotSupported;
-    {
-        const Tuning* at = active_tuning();
-        const int min_taps = at ? (inverse ? at->swt_split_inv : at->swt_split_fwd) : split_min(inverse).load(std::memory_order_relaxed);
-        if (stream_route32(a.hlen, a.Nr, a.Nc, a.f, inverse, (long long)batch * a.Nr * a.Nc, min_taps)) {
-            note_family("stream");
-            return stream_level2d(a, tmp, inverse, batch, s);
-        }
+    if (stream_route32(a.hlen, a.Nr, a.Nc, a.f, inverse, (long long)batch * a.Nr * a.Nc, split_min(inverse))) {
+        note_family("stream");
+        return stream_level2d(a, tmp, inverse, batch, s);
     }
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!al16(tmp) || !al16(a.A) || !al16(a.H) || !al16(a.V) || !al16(a.D) || (a.bstride & 3)) return hipErrorNotSupported;

@@ -2303,23 +2303,14 @@ int pdwt_device_of_pointer(const void* ptr) {
 }
 
 int pdwt_set_tuning(const char* key, int value) {
-    if (key && !strcmp(key, "wave_min_log2")) return set_wave_min_log2(value);
-    if (key && !strcmp(key, "dwt_split_fwd")) return set_dwt_split_min(0, value);
-    if (key && !strcmp(key, "dwt_split_inv")) return set_dwt_split_min(1, value);
-    if (key && !strcmp(key, "lds_max_log2")) return set_lds_max_log2(value);
-    if (key && !strcmp(key, "ring_min_log2")) return set_ring_min_log2(value);
-    if (key && !strcmp(key, "long_fwd")) return set_long_min_taps(0, value);
-    if (key && !strcmp(key, "long_inv")) return set_long_min_taps(1, value);
-    if (key && !strcmp(key, "swt_colstream")) return set_swt_colstream_min(value);
-    if (key && !strcmp(key, "swt_fwdstream")) return set_swt_fwdstream_min(value);
-    if (key && !strcmp(key, "swt_invstream")) return set_swt_invstream_min(value);
-    if (key && !strcmp(key, "wave2")) return set_wave2_enabled(value);
-    if (key && !strcmp(key, "reg1d")) return set_reg1d_enabled(value);
-    if (key && !strcmp(key, "swt_fused")) return set_swt_fused_enabled(value);
-    if (key && !strcmp(key, "chain")) return set_chain_enabled(value);
-    if (key && !strcmp(key, "swt_split_fwd")) return set_swt_split_min(0, value);
-    if (key && !strcmp(key, "swt_split_inv")) return set_swt_split_min(1, value);
-    if (key && !strcmp(key, "chain_timeout")) return set_chain_timeout(value);
+    static const char* const names[kKnobCount] = {  // the snapshot knobs: one row each of tuning_knobs.inc
+#define PDWT_KNOB(name, lo, hi, init, what) #name,
+#include "tuning_knobs.inc"
+#undef PDWT_KNOB
+    };
+    for (int k = 0; key && k < kKnobCount; ++k)
+        if (!strcmp(key, names[k])) return set_knob((Knob)k, value);
+    if (key && !strcmp(key, "chain_timeout")) return set_chain_timeout(value);  // not a dispatch knob, not part of the snapshot
     return fail(PDWT_ERR_ARG, "pdwt_set_tuning: unknown key %s", key ? key : "(null)");
 }
 

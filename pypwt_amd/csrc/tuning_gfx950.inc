@@ -6,7 +6,7 @@
 // files are summarised there); `measured` the round and date.  plan.cpp (build_schedule) and the launch_*.hip dispatchers read
 // the values as pdwt::tune::key (tuning.hpp); tools/tuning_table.py prints this file as the table of DESIGN.md and checks that
 // every evidence file exists; tools/retune.py re-measures the keys a process can move at run time (pdwt_set_tuning) and says
-// which rows a sweep would change.
+// which rows a sweep would change.  The run-time keys themselves ("tuning key ..." below) are the rows of tuning_knobs.inc.
 //
 // Rule for changing a value (VERDICT round 5, weak 6): an A/B may move a default only when the alternative wins by at least
 // 5 % on the measured plan, or by any margin on three different boxes -- box-to-box spread on 10-90 us plans is 2-10 %

@@ -392,3 +392,93 @@ def test_dispatch_thresholds_are_a_table_with_provenance():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "tuning_table.py")], capture_output=True, text=True).stdout
     doc = open(os.path.join(ROOT, "docs", "TUNING.md")).read()
     assert out.strip() and out.strip() in doc, "docs/TUNING.md is stale: regenerate its table with tools/tuning_table.py"
+
+
+# ---- the run-time knobs: pypwt_amd/csrc/tuning_knobs.inc
+
+KNOB_PROBES = (-5, -1, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)
+# RECORDED from the three libraries of the commit BEFORE the knobs became a table (each knob then had its own static, setter and
+# clamp): per key, the value the first pdwt_set_tuning(key, 0) of a fresh process returned in (f32, f64, lab), and the value
+# stored after setting each of KNOB_PROBES.  (chain_timeout: the product libraries stub the chain kernels out and keep nothing.)
+KNOB_RECORD = {
+    "wave_min_log2":  ((22, 16, 22), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 63, 63, 63, 63, 63)),
+    "lds_max_log2":   ((25, 0, 25), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 62, 62, 62, 62, 62, 62)),
+    "swt_split_fwd":  ((14, 12, 14), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "swt_split_inv":  ((10, 6, 10), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "dwt_split_fwd":  ((0, 28, 0), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "dwt_split_inv":  ((0, 28, 0), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "ring_min_log2":  ((25, 25, 25), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 63, 63, 63, 63, 63)),
+    "long_fwd":       ((18, 18, 18), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "long_inv":       ((18, 18, 18), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "swt_colstream":  ((10, 10, 10), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "swt_fwdstream":  ((6, 6, 6), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "swt_invstream":  ((6, 6, 6), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+    "wave2":          ((0, 0, 0), (1, 1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1)),
+    "swt_fused":      ((1, 1, 1), (0, 0, 0, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2)),
+    "chain":          ((0, 0, 0), (0, 0, 0, 1, 2, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3)),
+    "reg1d":          ((3, 3, 3), (0, 0, 0, 1, 2, 3, 4, 15, 15, 15, 15, 15, 15, 15, 15, 15)),
+    "chain_timeout":  ((0, 0, 3000), (0, 0, 0, 1, 2, 3, 4, 15, 16, 62, 63, 64, 99, 110, 140, 100000)),
+}
+KNOB_RECORD_STUBBED = {"chain_timeout": (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)}  # ... in (f32, f64)
+KNOB_VARIANTS = ("f32", "f64", "lab")
+
+
+def knob_rows():
+    """(key, lo, hi) of every row of tuning_knobs.inc, as tools/tuning_table.py reads tuning_gfx950.inc."""
+    inc = os.path.join(ROOT, "pypwt_amd", "csrc", "tuning_knobs.inc")
+    rows = [m.groups() for m in (re.match(r"^PDWT_KNOB\(\s*(\w+)\s*,\s*(\w+)\s*,\s*(\w+)\s*,", line) for line in open(inc)) if m]
+    assert sum(line.startswith("PDWT_KNOB") for line in open(inc)) == len(rows)
+    return rows
+
+
+def _knobs_of_a_fresh_process(variant, keys, probes=(), env=None):
+    """{key: [first pdwt_set_tuning(key, 0), [value stored after each probe]]} from a process that has moved nothing before."""
+    import json
+    import subprocess
+    import sys
+    from pypwt_amd.build import build_library
+    path = build_library(verbose=False, variant=variant)
+    code = ("import ctypes, json\n"
+            "f = ctypes.CDLL(%r).pdwt_set_tuning\n"
+            "f.restype, f.argtypes = ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]\n"
+            "out = {}\n"
+            "for k in %r:\n"
+            "    first, stored = f(k.encode(), 0), []\n"
+            "    for p in %r:\n"
+            "        f(k.encode(), p)\n"
+            "        stored.append(f(k.encode(), 0))\n"
+            "    out[k] = [first, stored]\n"
+            "print(json.dumps(out))\n" % (path, list(keys), list(probes)))
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("PDWT_")}  # (a developer's own A/B variables must not move a default)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(clean, **(env or {})))
+    assert r.returncode == 0, r.stderr
+    return json.loads(r.stdout)
+
+
+@pytest.mark.parametrize("variant", KNOB_VARIANTS)
+def test_knob_defaults_and_clamps_are_those_recorded_before_the_table(variant):
+    """Every default and every clamp of pdwt_set_tuning equals what the hand-written setters did (KNOB_RECORD)."""
+    got = _knobs_of_a_fresh_process(variant, KNOB_RECORD, KNOB_PROBES)
+    for key, (defaults, stored) in KNOB_RECORD.items():
+        if variant != "lab":
+            stored = KNOB_RECORD_STUBBED.get(key, stored)
+        assert got[key][0] == defaults[KNOB_VARIANTS.index(variant)], (variant, key, "default", got[key][0])
+        assert tuple(got[key][1]) == stored, (variant, key, got[key][1])
+
+
+def test_knob_initial_values_from_the_environment_are_masked_but_not_clamped():
+    """The measurement library reads its initial values from the environment as before: PDWT_REG1D keeps its `& 15`, a value
+    outside the setter's range stays as it is, PDWT_NO_WAVE wins over the default."""
+    got = _knobs_of_a_fresh_process("lab", ("reg1d", "swt_fused", "wave_min_log2"),
+                                    env={"PDWT_REG1D": "19", "PDWT_SWT_FUSED": "7", "PDWT_NO_WAVE": "1"})
+    assert [got[k][0] for k in ("reg1d", "swt_fused", "wave_min_log2")] == [3, 7, 63]
+
+
+def test_documented_tuning_keys_are_the_rows_of_the_knob_table():
+    """include/pypwt_amd_bench.h documents exactly the rows of tuning_knobs.inc and chain_timeout; no row twice."""
+    txt = open(os.path.join(ROOT, "include", "pypwt_amd_bench.h")).read()
+    doc = txt[txt.index("process-wide dispatch knobs"):txt.index("int pdwt_set_tuning")]
+    rows = [k for k, _, _ in knob_rows()]
+    assert len(rows) == len(set(rows)) == 16
+    assert set(re.findall(r'"([a-z0-9_]+)"', doc)) == set(rows) | {"chain_timeout"}
+    assert set(KNOB_RECORD) == set(rows) | {"chain_timeout"}

@@ -870,6 +870,87 @@ def test_plan_keeps_the_tuning_it_was_created_with():
         lib.pdwt_set_tuning(b"swt_fwdstream", prev_stream)
 
 
+# One case per translation unit that reads run-time knobs (tuning_knobs.inc) through knob(): library, {key: (forcing value, off, a value
+# neither plan has)}, knobs and environment held as the test that forces the key holds them, (wavelet, shape, levels, do_swt) -- the
+# smallest shape of that test --, the (launch name, family) pairs of the forced kernels (family None: any), and the forward / inverse
+# tolerance of that test as factors of max(|reference|, |image|) and of 255 (fp64: of max(|reference|, 1) and 255).
+SNAPSHOT_CASES = {
+    # launch_dwt2.hip -- tests/test_gpu_long.py
+    "long": ("f32", {"long_fwd": (110, 0, 140), "long_inv": (110, 0, 140)}, {}, ("PDWT_NO_PYRAMID", "PDWT_NO_TAIL"), ("db10", (64, 72), 1, 0),
+             [("dwt2_fwd_level", "long"), ("dwt2_inv_level", "long")], (2e-6 * 2, 2e-6 * 2)),
+    # launch_dwt2.hip -- tests/test_gpu_wave.py
+    "wave": ("f32", {"wave_min_log2": (0, 63, 30)}, {"lds_max_log2": 0}, ("PDWT_NO_PYRAMID",), ("haar", (2, 4), 1, 0),
+             [("dwt2_fwd_level", "wave"), ("dwt2_inv_level", "wave")], (2e-6 * 2, 2e-6 * 2)),
+    # launch_swt_fwdstream.hip, launch_swt_invstream.hip -- tests/test_gpu_fwdstream.py, tests/test_gpu_invstream.py
+    "swt_streams": ("f32", {"swt_fwdstream": (106, 0, 120), "swt_invstream": (106, 0, 120)}, {}, (), ("db3", (97, 36), 1, 1),
+                    [("swt2_fwd_stream", None), ("swt2_inv_stream", None)], (2e-6 * 2, 4e-6 * 2)),
+    # launch_swt_split.hip -- tests/test_gpu_colstream.py
+    "swt_colstream": ("f32", {"swt_colstream": (110, 0, 140)}, {"swt_split_fwd": 104, "swt_split_inv": 104, "swt_fwdstream": 0, "swt_invstream": 0}, (),
+                      ("db5", (97, 36), 1, 1), [("swt2_fwd_split", "colstream"), ("swt2_inv_split", "colstream")], (2e-6 * 2, 4e-6 * 2)),
+    # plan.cpp: build_schedule reads the snapshot -- tests/test_gpu_wave.py::test_swt_haar_levels_fused_per_launch_on_the_gpu
+    "swt_fused": ("f32", {"swt_fused": (1, 0, 2)}, {}, (), ("haar", (64, 256), 3, 1),
+                  [("swt2_fwd_fused", None), ("swt2_inv_fused", None)], (2e-6 * 4, 2e-3 / 255.0)),
+    # launch_dwt2_split.hip (fp64 library) -- tests/test_gpu_parity.py::test_fp64_decimated_stream_levels_forced_for_every_filter
+    "dwt_split_inv": ("f64", {"dwt_split_inv": (102, 0, 140)}, {}, (), ("db13", (200, 204), 3, 0), [("dwt2_inv_split", None)], (1e-12, 1e-11)),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(SNAPSHOT_CASES))
+def test_plan_keeps_every_knob_it_was_created_with(case):
+    """The single-threaded sibling of the test above for one key per translation unit that reads knobs: plan A is created with the
+    key at its forcing value, plan B with it off, then the key moves to a value neither has; A still runs the forced kernels, B runs
+    none of them, and both match the oracle."""
+    from pypwt_amd import BatchedWavelets, BatchedWavelets64, _lib
+    variant, keys, held, env, (wname, shape, levels, swt), forced_launches, (tol_fwd, tol_inv) = SNAPSHOT_CASES[case]
+    f64 = variant == "f64"
+    lib = _lib.load(variant)
+    x = oracle.hash_input(shape, 913, scale=255.0)
+    if f64:
+        x = x.astype(np.float64) + 1e-9 * (np.arange(x.size) % 997).reshape(x.shape)  # something fp32 cannot hold
+    prev = [(k, lib.pdwt_set_tuning(k.encode(), v)) for k, v in list(held.items()) + [(k, v[0]) for k, v in keys.items()]]
+    for name in env:  # read when a plan is created
+        os.environ[name] = "1"
+    try:
+        assert min(v for _, v in prev) >= 0
+
+        def plan():
+            return (BatchedWavelets64 if f64 else BatchedWavelets)(1, shape[0], shape[1], wname, levels, do_swt=swt, img=x[None])
+        A = plan()
+        for k, v in keys.items():
+            lib.pdwt_set_tuning(k.encode(), v[1])
+        B = plan()
+        for k, v in keys.items():
+            lib.pdwt_set_tuning(k.encode(), v[2])
+        dbl = {"double": "full"} if f64 else {}
+        ref = oracle.forward(x, wname, levels, do_swt=swt, **dbl)
+        want = oracle.inverse(ref, shape, wname, levels, do_swt=swt, **dbl)
+        floor = 1.0 if f64 else float(np.abs(x).max())  # (at most 255: never above the floor of the test the case comes from)
+        ran = {}
+        for tag, p in (("A", A), ("B", B)):
+            assert p.levels == levels
+            p.enable_kernel_timing(True)
+            p.reset_kernel_times()
+            p.forward()
+            p.inverse()
+            ran[tag] = list(zip([n for n, _ in p.kernel_times()], p.kernel_families()))
+            assert np.abs(p.image_at(0) - want).max() <= tol_inv * 255.0, (case, tag)
+            p.forward()
+            for k, r in enumerate(ref):
+                assert np.abs(p.coeff_at(k, 0) - r).max() <= tol_fwd * max(float(np.abs(r).max()), floor), (case, tag, k)
+
+        def hit(launch, which):
+            return any(n.split("+")[0] == launch[0] and launch[1] in (None, f) for n, f in ran[which])
+        for launch in forced_launches:
+            assert hit(launch, "A"), (case, launch, ran)
+            assert not hit(launch, "B"), (case, launch, ran)
+    finally:
+        for name in env:
+            os.environ.pop(name, None)
+        for k, v in reversed(prev):
+            lib.pdwt_set_tuning(k.encode(), v)
+
+
 @pytest.mark.gpu
 def test_bind_image_chains_two_plans_without_a_copy(W):
     """pdwt_bind_image: the image of a second plan IS band 0 of the first (no reference counterpart: the reference owns all of
