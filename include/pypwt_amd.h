@@ -314,6 +314,57 @@ int pdwt_comm_all_gather(pdwt_comm_handle c, const void* send, void* recv, long 
 int pdwt_comm_broadcast(pdwt_comm_handle c, void* buf, long long count, int root, void* hip_stream);
 const char* pdwt_comm_last_error(void);
 
+/* ---- NEW: 3D DWT of a volume [Nz][Nr][Nc] (C order).  No reference counterpart: "3D is not handled at the moment"
+ * (pdwt/README.md:29), the reference's constructor stops at "ndim=%d is not implemented" (pdwt/src/wt.cu:170-172).
+ * The separable decimated transform with the boundary rule of the rest of the library (an odd length is extended by repeating
+ * its last sample, and that extended signal is periodic: pywt's "periodization"), one level = a depth pass along z followed by
+ * one level of the batched 2D transform on the low and high slices.  div2(n) = (n + (n & 1)) / 2.
+ *   - levels are clamped by the reference's rule on the SMALLEST of the three sizes (wt.cu:155-165), with its warning;
+ *   - PDWT_ERR_ARG: a size below 2 on any axis, Nz > 65534 (the per-band operators take at most 65535 images, and a level
+ *     holds 2 div2(Nz) of them); PDWT_ERR_WAVELET: unknown name; PDWT_ERR_UNSUPPORTED: a filter of odd length (the built-in
+ *     table has none) -- all answered before any device call;
+ *   - coefficient index `num`: 0 = A_L, then 1 + 7 (l - 1) + k, level 1 the finest, k over the keys of pywt.wavedecn with axes
+ *     (z, y, x) in sorted order: aad, ada, add, daa, dad, dda, ddd ('a' low-pass, 'd' high-pass).  Every band is contiguous
+ *     [depth][rows][cols] with (div2^l Nz, div2^l Nr, div2^l Nc) at level l;
+ *   - the state machine is pdwt_state's: a second pdwt_volume_inverse in a row returns PDWT_ERR_STATE and does nothing;
+ *     pdwt_volume_get_coeff answers 0 after an inverse (like pdwt_get_coeff) and the thresholds and norms PDWT_ERR_STATE,
+ *     until pdwt_volume_set_coeff(num 0), pdwt_volume_set_image or pdwt_volume_forward;
+ *   - soft / hard threshold: pdwt_soft_threshold's / pdwt_hard_threshold's arithmetic and arguments, bit for bit: with
+ *     normalize the details of level l take beta / sqrt(2)^l and the approximation beta / sqrt(2)^L;
+ *   - pdwt_volume_norms: {sum |c|, sum c^2} over all coefficients, accumulated in double; blocks;
+ *   - footprint: about 3.3 volumes of device memory (the image, and per level the slice stack and its coefficients);
+ *   - pointers from pdwt_volume_image_ptr / pdwt_volume_coeff_ptr are borrowed and valid while the volume lives.
+ * pdwt_volume_layout is a pure host function (no device needed): the clamped level count into *nlevels, (depth, rows, cols) of
+ * num 0 .. capacity - 1 into dims[3 num + {0,1,2}]; returns the number of bands 1 + 7 L, or a negative status.
+ * Out of scope: 3D SWT, non-separable volumes, custom filter banks, cycle spinning, clone and add_wavelet, shrink / group /
+ * proj_linf, the adaptive and K-term operators on volumes, the compiled Cython class, ShardedBatch / TiledWavelets for volumes,
+ * a fused kernel that does all three axes in one read. */
+typedef struct pdwt_volume* pdwt_volume_handle;
+int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host,
+                       int device_id, void* hip_stream, pdwt_volume_handle* out); /* img NULL = zero volume; device_id < 0 = current; hip_stream NULL = private */
+int pdwt_volume_destroy(pdwt_volume_handle h);
+int pdwt_volume_forward(pdwt_volume_handle h);
+int pdwt_volume_inverse(pdwt_volume_handle h);
+int pdwt_volume_get_info(pdwt_volume_handle h, int* Nz, int* Nr, int* Nc, int* nlevels, int* hlen, int* state);
+int pdwt_volume_layout(int Nz, int Nr, int Nc, const char* wname, int levels, int* nlevels, int* dims, int capacity);
+long long pdwt_volume_get_image(pdwt_volume_handle h, pdwt_real* dst); /* returns element count, <0 on error */
+int pdwt_volume_set_image(pdwt_volume_handle h, const pdwt_real* src, int mem_is_on_device);
+long long pdwt_volume_get_coeff(pdwt_volume_handle h, pdwt_real* dst, int num); /* 0 if refused after inverse */
+int pdwt_volume_set_coeff(pdwt_volume_handle h, const pdwt_real* src, int num, int mem_is_on_device);
+long long pdwt_volume_coeff_count(pdwt_volume_handle h, int num, int* depth, int* rows, int* cols);
+intptr_t pdwt_volume_image_ptr(pdwt_volume_handle h);
+intptr_t pdwt_volume_coeff_ptr(pdwt_volume_handle h, int num);
+int pdwt_volume_soft_threshold(pdwt_volume_handle h, pdwt_real beta, int do_thresh_appcoeffs, int normalize);
+int pdwt_volume_hard_threshold(pdwt_volume_handle h, pdwt_real beta, int do_thresh_appcoeffs, int normalize);
+int pdwt_volume_norms(pdwt_volume_handle h, double out[2]);
+int pdwt_volume_synchronize(pdwt_volume_handle h);
+void* pdwt_volume_stream(pdwt_volume_handle h);
+/* how the depth passes of level `level` (1 .. nlevels) are launched, fixed when the volume is created: columns per thread (16 B or,
+ * from 18 taps on, 8 B per lane where the plane size allows it, else 1) and the steps a workgroup walks per depth segment, forward
+ * and inverse (one step = one low and one high slice forward, two output slices inverse).  Any pointer may be NULL.  Diagnostics,
+ * like pdwt_schedule_string for a 2D plan. */
+int pdwt_volume_depth_schedule(pdwt_volume_handle h, int level, int* width, int* seg_fwd, int* seg_inv);
+
 #ifdef __cplusplus
 }
 #endif

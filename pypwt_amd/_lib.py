@@ -124,6 +124,26 @@ def signatures(real=C.c_float):
         "pdwt_comm_all_gather": (C.c_int, [handle_t, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
         "pdwt_comm_broadcast": (C.c_int, [handle_t, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
         "pdwt_comm_last_error": (C.c_char_p, []),
+        "pdwt_volume_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.POINTER(handle_t)]),
+        "pdwt_volume_destroy": (C.c_int, [handle_t]),
+        "pdwt_volume_forward": (C.c_int, [handle_t]),
+        "pdwt_volume_inverse": (C.c_int, [handle_t]),
+        "pdwt_volume_get_info": (C.c_int, [handle_t] + [C.POINTER(C.c_int)] * 6),
+        "pdwt_volume_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+        "pdwt_volume_get_image": (C.c_longlong, [handle_t, C.c_void_p]),
+        "pdwt_volume_set_image": (C.c_int, [handle_t, C.c_void_p, C.c_int]),
+        "pdwt_volume_get_coeff": (C.c_longlong, [handle_t, C.c_void_p, C.c_int]),
+        "pdwt_volume_set_coeff": (C.c_int, [handle_t, C.c_void_p, C.c_int, C.c_int]),
+        "pdwt_volume_coeff_count": (C.c_longlong, [handle_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "pdwt_volume_image_ptr": (C.c_ssize_t, [handle_t]),
+        "pdwt_volume_coeff_ptr": (C.c_ssize_t, [handle_t, C.c_int]),
+        "pdwt_volume_soft_threshold": (C.c_int, [handle_t, real, C.c_int, C.c_int]),
+        "pdwt_volume_hard_threshold": (C.c_int, [handle_t, real, C.c_int, C.c_int]),
+        "pdwt_volume_norms": (C.c_int, [handle_t, C.POINTER(C.c_double)]),
+        "pdwt_volume_synchronize": (C.c_int, [handle_t]),
+        "pdwt_volume_stream": (C.c_void_p, [handle_t]),
+        "pdwt_volume_depth_schedule": (C.c_int, [handle_t, C.c_int] + [C.POINTER(C.c_int)] * 3),
     }
 
 

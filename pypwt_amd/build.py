@@ -46,6 +46,7 @@ SOURCES = [
     "launch_dwt2_wave.hip",
     "launch_dwt2_ring.hip",
     "launch_dwt2_long.hip",
+    "launch_dwt3.hip",
     "launch_dwt1.hip",
     "launch_dwt1_fused.hip",
     "launch_dwt1_reg.hip",
@@ -59,6 +60,7 @@ SOURCES = [
     "launch_ops.hip",
     "launch_nonsep.hip",
     "plan.cpp",
+    "volume.cpp",
     "comm.cpp",
     "wavelet_table.cpp",
 ]

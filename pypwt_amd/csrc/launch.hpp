@@ -125,6 +125,18 @@ hipError_t launch_dwt2_tail(const real_t* in, real_t* const* det, real_t* out, i
 bool swt2_tail_supported(int hlen, int Nr, int Nc, int L);
 hipError_t launch_swt2_tail(const real_t* in, real_t* const* det, real_t* out, int Nr, int Nc, int L, int hlen, bool inverse,
                             const FilterBank& fb, const real_t* beta, int batch, hipStream_t s);
+// one decimated level along the slowest axis of a volume (dwt3_axis_kernels.hpp): forward in [Nz][P] -> out [2 div2(Nz)][P] (low
+// slices, then high slices); inverse the other way round (Nz = the OUTPUT's depth).  Even hlen of the built-in table; seg = steps per
+// depth segment, from dwt3_depth_seg (slots = workgroups the chip keeps resident) for the width dwt3_depth_width answers: columns
+// per thread, 16 B (8 B from 18 taps on) where P and both addresses allow it, else 1
+int dwt3_depth_width(const void* in, const void* out, long long P, int hlen);
+int dwt3_depth_steps(int Nz, int hlen, bool inverse);
+int dwt3_depth_seg(int Nz, long long P, int hlen, int width, bool inverse, int slots);
+int dwt3_depth_slots(int hlen, int width, bool inverse);  // resident workgroups of that kernel on the current device (occupancy x CUs)
+hipError_t launch_dwt3_depth_fwd(const real_t* in, real_t* out, int Nz, long long P, int hlen, const FilterBank& fb, int seg,
+                                 hipStream_t s);
+hipError_t launch_dwt3_depth_inv(const real_t* in, real_t* out, int Nz, long long P, int hlen, const FilterBank& fb, int seg,
+                                 hipStream_t s);
 hipError_t launch_dwt1_fwd(const Fwd1DArgs& a, hipStream_t s);
 hipError_t launch_dwt1_inv(const Inv1DArgs& a, hipStream_t s);
 // K consecutive 1D levels in one launch (2^K must divide N0, even hlen); hipErrorNotSupported otherwise

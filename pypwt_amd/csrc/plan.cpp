@@ -1492,6 +1492,16 @@ std::string info_text(pdwt_plan* p) {
 
 }  // namespace
 
+int pdwt::set_last_error(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_last_error = buf;
+    return code;
+}
+
 // =============================================================================
 #pragma GCC visibility push(default)
 extern "C" {

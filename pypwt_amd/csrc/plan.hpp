@@ -81,6 +81,9 @@ struct LazyThreshold {
     int normalize = 0;
 };
 
+// the calling thread's pdwt_last_error() message, for the entry points that live outside plan.cpp (volume.cpp); returns `code`
+int set_last_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
 }  // namespace pdwt
 
 struct pdwt_plan {

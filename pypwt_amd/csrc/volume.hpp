@@ -1,0 +1,36 @@
+// volume.hpp -- host-side 3D DWT of a volume [Nz][Nr][Nc] (pdwt_volume_* of include/pypwt_amd.h).
+//
+// No reference counterpart: "3D is not handled at the moment" (pdwt/README.md:29), the constructor stops at
+// "ndim=%d is not implemented" (pdwt/src/wt.cu:170-172).
+//
+// One level = the depth pass (dwt3_axis_kernels.hpp) followed by ONE level of the batched 2D transform on the stack of low and
+// high slices it wrote.  A volume owns its image and one batched 2D plan per level (batch = 2 div2(Nz_l), levels = 1):
+//
+//   image [Nz][Nr][Nc]
+//   level l:  plan_l's image slot  = the stack [2 div2(Nz_{l-1})][Nr_{l-1}][Nc_{l-1}] the depth pass writes
+//             plan_l's bands A,H,V,D, each [batch][div2 Nr][div2 Nc]: the first half of the images of a band is its depth-low
+//             sub-band, the second half its depth-high one -- the eight 3D sub-bands are views, nothing is copied.
+//             The depth-low half of band A is A_l: the next level's depth pass reads it in place; for l < L it is an
+//             intermediate, for l = L the coefficient num 0.
+//
+// Footprint: about 3.3 volumes -- the image, and per level a stack plus a coefficient region of that level's size
+// (1 + 2 (1 + 1/8 + 1/64 + ...)).  Not shaved here.
+#pragma once
+
+#include <vector>
+
+#include "plan.hpp"
+
+struct pdwt_volume {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int Nz = 0, Nr = 0, Nc = 0, nlevels = 0, hlen = 0;
+    int state = PDWT_INIT;
+    char wname[128] = {0};
+    real_t* image = nullptr;            // [Nz][Nr][Nc], owned
+    std::vector<pdwt_handle> plans;     // [l - 1]: the batched 2D plan of level l; plans[0] owns the stream unless the caller gave one
+    std::vector<int> nz, nr, nc;        // [l]: sizes of A_l, [0] = the image
+    std::vector<int> seg_fwd, seg_inv;  // [l - 1]: steps per depth segment of level l's depth passes
+    std::vector<int> width;             // [l - 1]: columns per thread of level l's depth passes
+    pdwt::FilterBank dec{}, rec{};
+};

@@ -1,0 +1,246 @@
+"""`Wavelets3D`: the separable decimated 3D DWT of a volume on the GPU (the pdwt_volume_* block of include/pypwt_amd.h).
+
+The reference stops at two dimensions ("3D is not handled at the moment", pdwt/README.md:29); this class follows the 2D
+`Wavelets` in everything that carries over -- level clamping, state rules, thresholds, norms -- with the boundary rule of the
+rest of the library (pywt's "periodization").  ctypes binding only.
+
+    W = Wavelets3D(vol, "db2", 3); W.forward(); W.soft_threshold(10); W.inverse(); W.coeffs; W.image
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, handle_t
+from .wavelets import DeviceArray, _device_array, _ptr
+
+KEYS = ("aad", "ada", "add", "daa", "dad", "dda", "ddd")  # pywt.wavedecn's keys with axes (z, y, x), sorted: the order of `num`
+
+
+def volume_layout(shape, wname, levels, lib=None):
+    """(levels after clamping, [(depth, rows, cols) of every coefficient index]) of a volume of `shape`: a pure host
+    computation (pdwt_volume_layout), no device needed."""
+    lib = lib or _lib.load()
+    nz, nr, nc = (int(n) for n in shape)
+    nlev = C.c_int(0)
+    cap = 1 + 7 * max(int(levels), 1)
+    dims = (C.c_int * (3 * cap))()
+    n = check(lib.pdwt_volume_layout(nz, nr, nc, wname.encode("ascii"), int(levels), C.byref(nlev), dims, cap), "volume_layout", lib)
+    return nlev.value, [tuple(dims[3 * k:3 * k + 3]) for k in range(n)]
+
+
+class Wavelets3D(object):
+    """3D DWT plan of one volume [Nz][Nr][Nc].
+
+    vol : C-contiguous 3D numpy array of the instance's dtype (float32), or a device array / torch tensor on the GPU
+          (``__cuda_array_interface__``), copied device-to-device
+    wname, levels : as for `Wavelets`; the levels are clamped by the reference's rule on the smallest of the three sizes
+    device : device ordinal, -1 = the current one;  stream : a HIP stream handle to run on, None = a private stream
+
+    Coefficient index ``num``: 0 = the approximation A_L, then 1 + 7 (l - 1) + k with level 1 the FINEST and k over the keys
+    'aad', 'ada', 'add', 'daa', 'dad', 'dda', 'ddd' -- pywt.wavedecn's, axes (z, y, x).  ``coeffs`` is ``[A, d_1, ..., d_L]``
+    with every d_l a dict over those keys; pywt.wavedecn's order is ``[c[0]] + c[:0:-1]``.
+    """
+    _variant = "f32"
+    _dtype = np.float32
+
+    def __init__(self, vol, wname, levels, device=-1, stream=None):
+        self._h = None
+        self._lib = _lib.load(self._variant)
+        dev = _device_array(vol, self._dtype)
+        if dev is not None:
+            shape = dev[1]
+        else:
+            vol = np.asarray(vol)
+            shape = vol.shape
+        if len(shape) != 3:
+            raise ValueError("Wavelets3D: the volume must have three dimensions, got shape %s" % (shape,))
+        if dev is None:
+            vol = self._checkarray(vol, shape)
+        self.shape = tuple(int(n) for n in shape)
+        self.wname = wname
+        h = handle_t()
+        if dev is not None:
+            self._order_producer(dev, device)
+        src = C.c_void_p(dev[0]) if dev is not None else _ptr(vol)
+        check(self._lib.pdwt_volume_create(src, self.shape[0], self.shape[1], self.shape[2], wname.encode("ascii"), int(levels),
+                                           0 if dev is not None else 1, int(device), C.c_void_p(stream) if stream else None,
+                                           C.byref(h)), "Wavelets3D", self._lib)
+        self._h = h
+        self.levels = self.info()["nlevels"]
+        self.hlen = self.info()["hlen"]
+        self._shapes = volume_layout(self.shape, wname, self.levels, self._lib)[1]
+
+    # ---- helpers
+    def _check(self, rc, what=""):
+        return check(rc, what, self._lib)
+
+    @classmethod
+    def _checkarray(cls, arr, shp):
+        if arr.dtype != cls._dtype or not arr.flags["C_CONTIGUOUS"]:
+            raise ValueError("Wavelets3D: the array must be C-contiguous %s" % np.dtype(cls._dtype).name)
+        if tuple(arr.shape) != tuple(shp):
+            raise ValueError("The array does not have the correct shape (expected %s, got %s)" % (str(tuple(shp)), str(arr.shape)))
+        return arr
+
+    def _order_producer(self, dev, device=None):
+        """A device source is copied on the volume's own stream: order the copy after the source's producer."""
+        if not dev[2]:
+            return
+        if dev[2][0] == "stream":
+            self._check(self._lib.pdwt_sync_producer(-1, C.c_void_p(dev[2][1]), 0))
+        else:
+            owner = int(self._lib.pdwt_device_of_pointer(C.c_void_p(dev[0])))
+            self._check(self._lib.pdwt_sync_producer(owner if owner >= 0 else -1, None, 1))
+
+    def _source(self, arr, shp):
+        dev = _device_array(arr, self._dtype)
+        if dev is not None:
+            if tuple(dev[1]) != tuple(int(n) for n in shp):  # the exact shape, as for host arrays: nothing is reinterpreted
+                raise ValueError("The array does not have the correct shape (expected %s, got %s)" % (str(tuple(shp)), str(dev[1])))
+            self._order_producer(dev)
+            return C.c_void_p(dev[0]), 1
+        arr = self._checkarray(np.asarray(arr), shp)
+        return _ptr(arr), 0  # (the upload has finished when the call returns: nothing to keep alive)
+
+    # ---- introspection
+    def info(self):
+        v = [C.c_int() for _ in range(6)]
+        self._check(self._lib.pdwt_volume_get_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("Nz", "Nr", "Nc", "nlevels", "hlen", "state"), (x.value for x in v)))
+
+    def __repr__(self):
+        return "<%s %s %s levels=%d>" % (type(self).__name__, "x".join(str(n) for n in self.shape), self.wname, self.levels)
+
+    def depth_schedule(self, level):
+        """(columns per thread, steps per depth segment forward, inverse) of the depth passes of `level` (1 .. levels)."""
+        v = [C.c_int() for _ in range(3)]
+        self._check(self._lib.pdwt_volume_depth_schedule(self._h, int(level), *[C.byref(x) for x in v]), "depth_schedule")
+        return tuple(x.value for x in v)
+
+    def band_shape(self, num):
+        return self._shapes[num]
+
+    @property
+    def nbands(self):
+        return len(self._shapes)
+
+    # ---- transforms
+    def forward(self, vol=None):
+        """Forward transform of ``vol`` if given, else of the current image."""
+        if vol is not None:
+            self.set_image(vol)
+        self._check(self._lib.pdwt_volume_forward(self._h), "forward")
+
+    def inverse(self):
+        """Coefficients -> ``image``.  As for `Wavelets`, a second call in a row does nothing but warn, and the coefficients
+        cannot be read or thresholded afterwards until forward() (or set_coeff of the approximation)."""
+        rc = self._lib.pdwt_volume_inverse(self._h)
+        if rc == _lib.ERR_STATE:
+            print("Warning: " + _lib.last_error(self._lib))
+            return
+        self._check(rc, "inverse")
+
+    # ---- data
+    @property
+    def image(self):
+        res = np.zeros(self.shape, dtype=self._dtype)
+        n = self._lib.pdwt_volume_get_image(self._h, _ptr(res))
+        if n != res.size:
+            raise RuntimeError("Wavelets3D.image: expected %d values, got %d (%s)" % (res.size, n, _lib.last_error(self._lib)))
+        return res
+
+    def set_image(self, vol):
+        """Replace the image (the coefficients are not updated; run forward())."""
+        src, on_device = self._source(vol, self.shape)
+        self._check(self._lib.pdwt_volume_set_image(self._h, src, on_device), "set_image")
+
+    def coeff_only(self, num):
+        """One sub-band as a numpy array [depth][rows][cols]."""
+        if num < 0 or num >= self.nbands:
+            raise ValueError("Wavelets3D.coeff_only: coefficient index %d out of range (0 .. %d)" % (num, self.nbands - 1))
+        res = np.zeros(self._shapes[num], dtype=self._dtype)
+        n = self._lib.pdwt_volume_get_coeff(self._h, _ptr(res), int(num))
+        if n != res.size:
+            raise RuntimeError("Wavelets3D.coeff_only: expected %d values, got %d (%s)" % (res.size, n, _lib.last_error(self._lib)))
+        return res
+
+    @property
+    def coeffs(self):
+        """``[A, d_1, ..., d_L]``: d_l is a dict keyed 'aad' ... 'ddd', level 1 the finest (pywt.wavedecn: ``[c[0]] + c[:0:-1]``)."""
+        out = [self.coeff_only(0)]
+        for l in range(1, self.levels + 1):
+            out.append({k: self.coeff_only(1 + 7 * (l - 1) + i) for i, k in enumerate(KEYS)})
+        return out
+
+    def set_coeff(self, arr, num):
+        """Overwrite one sub-band from a host array or a device array of its shape."""
+        if num < 0 or num >= self.nbands:
+            raise ValueError("Wavelets3D.set_coeff: coefficient index %d out of range (0 .. %d)" % (num, self.nbands - 1))
+        src, on_device = self._source(arr, self._shapes[num])
+        self._check(self._lib.pdwt_volume_set_coeff(self._h, src, int(num), on_device), "set_coeff")
+
+    # ---- operators
+    def _threshold(self, fn, beta, do_threshold_appcoeffs, normalize):
+        rc = fn(self._h, float(beta), int(do_threshold_appcoeffs), int(normalize))
+        if rc == _lib.ERR_STATE:
+            print("Warning: Wavelets3D(): " + _lib.last_error(self._lib))
+            return
+        self._check(rc)
+
+    def soft_threshold(self, beta, do_threshold_appcoeffs=0, normalize=0):
+        """sign(x) (|x| - t)_+ on the details (and on the approximation with ``do_threshold_appcoeffs``); ``normalize``: t is
+        divided by sqrt(2) at each scale."""
+        self._threshold(self._lib.pdwt_volume_soft_threshold, beta, do_threshold_appcoeffs, normalize)
+
+    def hard_threshold(self, beta, do_threshold_appcoeffs=0, normalize=0):
+        """x 1_{|x| > t}"""
+        self._threshold(self._lib.pdwt_volume_hard_threshold, beta, do_threshold_appcoeffs, normalize)
+
+    def norms(self):
+        """(sum |c|, sum c^2) over all coefficients, accumulated in float64."""
+        out = (C.c_double * 2)()
+        self._check(self._lib.pdwt_volume_norms(self._h, out), "norms")
+        return float(out[0]), float(out[1])
+
+    def norm1(self):
+        return self.norms()[0]
+
+    def norm2sq(self):
+        return self.norms()[1]
+
+    # ---- device views
+    def _stream(self):
+        return self._lib.pdwt_volume_stream(self._h) or 0
+
+    @property
+    def image_device(self):
+        """Zero-copy `DeviceArray` view of the image."""
+        return DeviceArray(self, self._lib.pdwt_volume_image_ptr(self._h), self.shape, self._dtype, self._stream())
+
+    def coeff_device(self, num):
+        """Zero-copy `DeviceArray` view of one sub-band [depth][rows][cols]."""
+        ptr = self._lib.pdwt_volume_coeff_ptr(self._h, int(num))
+        if not ptr:
+            raise ValueError("Wavelets3D.coeff_device: coefficient index %d out of range" % num)
+        return DeviceArray(self, ptr, self._shapes[num], self._dtype, self._stream())
+
+    def synchronize(self):
+        self._check(self._lib.pdwt_volume_synchronize(self._h))
+
+    def cleanup(self):
+        if getattr(self, "_h", None):
+            self._lib.pdwt_volume_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.cleanup()
+        except Exception:
+            pass
+
+
+class Wavelets3D64(Wavelets3D):
+    """The same on libpypwt_amd_f64.so: float64 volumes and coefficients."""
+    _variant = "f64"
+    _dtype = np.float64

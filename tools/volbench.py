@@ -1,0 +1,195 @@
+#!/usr/bin/env python3
+"""Times the 3D DWT of volumes (pypwt_amd.Wavelets3D) on the GPU.  Does not touch bench.py.
+
+    python tools/volbench.py                       > profiles/volume_bench.txt     end-to-end times, device events
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/volbench.py --profile --case N
+    python tools/volbench.py --summarize DIR --case N  > profiles/volume_rocprofv3_summary_<case>.txt
+
+Default mode: per case forward, inverse and forward + soft threshold + inverse, each timed TWICE in the same call (the
+spread) by two HIP events on the volume's stream around `--reps` calls (at least 50) after a warm-up of the same shapes.
+Beside them the yardstick of the same run: the flat copy of the same bytes (pdwt_time_copy of a BatchedWavelets that holds the
+level-1 slice stack) and the share of it that this plan's own level-1 2D kernel reaches (pdwt_time_level).  Gsamples/s and
+the bytes moved per sample are computed from the shapes.
+
+--profile: a short run of ONE case with one level (so that every kernel name in the trace belongs to level 1) plus the copy and
+the 2D level of the same bytes, for rocprofv3; --summarize reads the kernel trace of such a run and reports, per depth kernel,
+its share of the copy next to the share the 2D level-1 kernel reaches.
+"""
+import argparse
+import csv
+import ctypes as C
+import glob
+import os
+import re
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+# (name, shape, wavelet, levels)
+CASES = [("256^3 haar", (256, 256, 256), "haar", 3), ("256^3 db4", (256, 256, 256), "db4", 3), ("256^3 db20", (256, 256, 256), "db20", 3),
+         ("512^3 haar", (512, 512, 512), "haar", 3), ("512^3 db4", (512, 512, 512), "db4", 3), ("512^3 db20", (512, 512, 512), "db20", 3),
+         ("512x511x511 db4", (512, 511, 511), "db4", 3)]
+
+
+def div2(n):
+    return (n + (n & 1)) // 2
+
+
+def bytes_per_sample(shape, levels, itemsize=4):
+    """Bytes one direction of the composed transform moves per input sample: per level the depth pass reads A_{l-1} and writes
+    the stack, the 2D level reads the stack and writes its four bands."""
+    total, s = 0, shape
+    for _ in range(levels):
+        vol = s[0] * s[1] * s[2]
+        stack = 2 * div2(s[0]) * s[1] * s[2]
+        bands = 4 * 2 * div2(s[0]) * div2(s[1]) * div2(s[2])
+        total += itemsize * (vol + stack + stack + bands)
+        s = tuple(div2(n) for n in s)
+    return total / float(shape[0] * shape[1] * shape[2])
+
+
+class Events(object):
+    def __init__(self):
+        self.hip = C.CDLL("libamdhip64.so")
+        self.hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+        self.hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+        self.hip.hipEventSynchronize.argtypes = [C.c_void_p]
+        self.hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+        self.a, self.b = C.c_void_p(), C.c_void_p()
+        assert self.hip.hipEventCreate(C.byref(self.a)) == 0 and self.hip.hipEventCreate(C.byref(self.b)) == 0
+
+    def time(self, stream, fn, reps, warmup):
+        for _ in range(warmup):
+            fn()
+        assert self.hip.hipEventRecord(self.a, C.c_void_p(stream)) == 0
+        for _ in range(reps):
+            fn()
+        assert self.hip.hipEventRecord(self.b, C.c_void_p(stream)) == 0
+        assert self.hip.hipEventSynchronize(self.b) == 0
+        ms = C.c_float()
+        assert self.hip.hipEventElapsedTime(C.byref(ms), self.a, self.b) == 0
+        return ms.value / reps
+
+
+def make_volume(shape, wname, levels):
+    from pypwt_amd import Wavelets3D
+    rng = np.random.default_rng(1)
+    x = (rng.random(shape, dtype=np.float32) * np.float32(255.0))
+    return Wavelets3D(x, wname, levels)
+
+
+def variants(W):
+    lib, h = W._lib, W._h
+
+    def fwd():
+        assert lib.pdwt_volume_forward(h) == 0
+
+    def inv():  # the coefficients are declared current again in place (no copy, no device work), then the inverse runs
+        assert lib.pdwt_volume_set_coeff(h, C.c_void_p(lib.pdwt_volume_coeff_ptr(h, 0)), 0, 1) == 0
+        assert lib.pdwt_volume_inverse(h) == 0
+
+    def denoise():
+        assert lib.pdwt_volume_forward(h) == 0
+        assert lib.pdwt_volume_soft_threshold(h, 10.0, 0, 0) == 0
+        assert lib.pdwt_volume_inverse(h) == 0
+
+    return [("forward", fwd, 1), ("inverse", inv, 1), ("fwd+soft+inv", denoise, 2)]
+
+
+def yardstick(shape, wname, reps):
+    """(copy ms, 2D level-1 forward ms, inverse ms) of the level-1 slice stack as a one-level batched 2D plan."""
+    from pypwt_amd import BatchedWavelets
+    B = BatchedWavelets(2 * div2(shape[0]), shape[1], shape[2], wname, 1)
+    B.fill_hash(3)
+    B.forward()
+    elems = 2 * div2(shape[0]) * shape[1] * shape[2]
+    out = (B.time_copy(elems, reps), B.time_level(1, False, reps), B.time_level(1, True, reps), B.time_copy(elems, reps))
+    B.cleanup()
+    return tuple(us / 1e3 for us in out)  # the plan reports microseconds
+
+
+def run_bench(args):
+    ev = Events()
+    print("# volbench: 3D DWT end to end, fp32, %d calls per timing after %d warm-up calls; every variant timed twice" % (args.reps, args.warmup))
+    print("# %-18s %-13s %10s %10s %12s %10s" % ("case", "variant", "ms (1st)", "ms (2nd)", "Gsamples/s", "B/sample"))
+    for k, (name, shape, wname, levels) in enumerate(CASES):
+        if args.case is not None and k != args.case:
+            continue
+        W = make_volume(shape, wname, levels)
+        W.forward()
+        n = shape[0] * shape[1] * shape[2]
+        bps = bytes_per_sample(shape, W.levels)
+        for vname, fn, directions in variants(W):
+            t = [ev.time(W._stream(), fn, args.reps, args.warmup) for _ in range(2)]
+            print("  %-18s %-13s %10.4f %10.4f %12.2f %10.1f" % (name, vname, t[0], t[1], directions * n / (min(t) * 1e6), bps * directions))
+        W.cleanup()
+        c0, f1, i1, c1 = yardstick(shape, wname, args.reps)
+        print("  %-18s yardstick: copy of the level-1 stack %.4f / %.4f ms; 2D level-1 forward %.4f ms = %.2f of the copy, inverse %.4f ms = %.2f"
+              % (name, c0, c1, f1, min(c0, c1) / f1, i1, min(c0, c1) / i1))
+        sys.stdout.flush()
+
+
+def run_profile(args):
+    name, shape, wname, _ = CASES[args.case]
+    W = make_volume(shape, wname, 1)
+    vs = dict((v[0], v[1]) for v in variants(W))
+    for _ in range(args.reps):
+        vs["forward"]()
+        vs["inverse"]()
+    W.synchronize()
+    W.cleanup()
+    print("profiled", name, "levels=1", yardstick(shape, wname, args.reps))
+
+
+def run_summarize(args):
+    name, shape, wname, _ = CASES[args.case]
+    files = glob.glob(os.path.join(args.summarize, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        raise SystemExit("no *kernel_trace.csv under " + args.summarize)
+    dur = {}
+    for f in files:
+        for row in csv.DictReader(open(f)):
+            k = re.sub(r"^void |pdwt::|\(.*$", "", row["Kernel_Name"])
+            dur.setdefault(k, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1000.0)
+    print("# %s, one level: kernel trace, us per launch (n, mean, median, min)" % name)
+    med = {}
+    for k, v in sorted(dur.items(), key=lambda kv: -sum(kv[1])):
+        v = sorted(v)
+        med[k] = v[len(v) // 2]
+        print("  %-50s n=%4d mean=%9.2f med=%9.2f min=%9.2f" % (k, len(v), sum(v) / len(v), med[k], v[0]))
+    copy = [m for k, m in med.items() if k.startswith("copy_kernel")]
+    if not copy:
+        raise SystemExit("no copy_kernel in the trace")
+    copy = min(copy)
+    print("# share of the flat copy of the same bytes (copy median %.2f us): copy / kernel" % copy)
+    for k, m in sorted(med.items()):
+        if k.startswith("dwt3_depth") or k.startswith("dwt2_"):
+            print("  %-50s %.2f" % (k, copy / m))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--case", type=int, default=None)
+    ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--summarize", default=None)
+    ap.add_argument("--list", action="store_true")
+    args = ap.parse_args()
+    if args.list:
+        for k, c in enumerate(CASES):
+            print(k, c, "bytes/sample per direction %.1f" % bytes_per_sample(c[1], c[3]))
+        return
+    if args.summarize:
+        run_summarize(args)
+    elif args.profile:
+        run_profile(args)
+    else:
+        run_bench(args)
+
+
+if __name__ == "__main__":
+    main()
