@@ -337,8 +337,8 @@ const char* pdwt_comm_last_error(void);
  * pdwt_volume_layout is a pure host function (no device needed): the clamped level count into *nlevels, (depth, rows, cols) of
  * num 0 .. capacity - 1 into dims[3 num + {0,1,2}]; returns the number of bands 1 + 7 L, or a negative status.
  * Out of scope: 3D SWT, non-separable volumes, custom filter banks, cycle spinning, clone and add_wavelet, shrink / group /
- * proj_linf, the adaptive and K-term operators on volumes, the compiled Cython class, ShardedBatch / TiledWavelets for volumes,
- * a fused kernel that does all three axes in one read. */
+ * proj_linf, the compiled Cython class, ShardedBatch / TiledWavelets for volumes, a fused kernel that does all three axes in
+ * one read, a fused stats + threshold sweep. */
 typedef struct pdwt_volume* pdwt_volume_handle;
 int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host,
                        int device_id, void* hip_stream, pdwt_volume_handle* out); /* img NULL = zero volume; device_id < 0 = current; hip_stream NULL = private */
@@ -364,6 +364,41 @@ void* pdwt_volume_stream(pdwt_volume_handle h);
  * and inverse (one step = one low and one high slice forward, two output slices inverse).  Any pointer may be NULL.  Diagnostics,
  * like pdwt_schedule_string for a 2D plan. */
 int pdwt_volume_depth_schedule(pdwt_volume_handle h, int level, int* width, int* seg_fwd, int* seg_inv);
+
+/* The adaptive and the K-term operators (pdwt_band_stats_async ... pdwt_keep_largest_async above) on a volume.  A volume is ONE
+ * image: its bands are the 1 + 7 L sub-bands in `num` order, the slices and levels of a sub-band are pooled on the device, and the
+ * depth-low half of band A of every level below L -- an intermediate, not a coefficient -- is neither read nor written.  Everything
+ * is enqueued on the volume's stream and nothing waits for the host (pdwt_volume_read does).
+ *   - band_stats: d_out[num][2] = {sum |c|, sum c^2} of every sub-band as doubles in device memory (NULL: the volume's own slot),
+ *     accumulated in double in a fixed order without float atomics: two calls give the same bits;
+ *   - norms_async: d_out2[2] = the fixed-order sum of those rows (NULL: the row behind the last sub-band of the d_stats slot);
+ *     pdwt_volume_norms above is unchanged;
+ *   - estimate_sigma: d_out[1] = median(|ddd_1|) / 0.6744897501960817 over the WHOLE finest ddd sub-band (num 7), exact;
+ *     skimage.restoration.denoise_wavelet's rule for n-D data; skip_zeros leaves exact zeros out of the median;
+ *   - threshold_bands: table[num] of pdwt_real, 1 + 7 L entries in host or device memory, NaN = leave that sub-band alone, entry 0
+ *     is A_L; results are bit for bit those of pdwt_volume_soft_threshold / pdwt_volume_hard_threshold with that threshold;
+ *   - denoise: method and op as for pdwt_denoise_async; the BayesShrink mean is over the sub-band's elements, VisuShrink is
+ *     sigma sqrt(2 ln(Nz Nr Nc)); sigma NULL = estimate it; the table (NaN at index 0) and sigma stay in the slots;
+ *   - select_magnitude / keep_largest: pdwt_select_magnitude_async's rules with S = the 7 L detail sub-bands (plus A_L with
+ *     do_thresh_appcoeffs) and N their element count: the key is the bit pattern of |c|, NaNs sort behind +inf, K is clamped to
+ *     [0, N], K = 0 gives (+inf, 0), K >= N gives (0, N), ties with the K-th all survive, survivors stay bit for bit and the
+ *     rest become +0.0.  d_threshold / d_kept: device memory, NULL = the volume's slots;
+ *   - PDWT_ERR_ARG: a null handle, a negative K, a null table, an unknown op or method; PDWT_ERR_UNSUPPORTED, before anything is
+ *     launched: N >= 2^32, or a noise band of that size; PDWT_ERR_STATE after pdwt_volume_inverse, with nothing done: the read-only
+ *     calls as pdwt_volume_norms, the sweeps (threshold_bands, denoise, keep_largest) as the thresholds;
+ *   - the slots are borrowed device pointers, valid while the volume lives, allocated by the first call that needs them;
+ *     pdwt_volume_read copies `bytes` from device memory to the host on the volume's stream and waits for it. */
+int pdwt_volume_band_stats_async(pdwt_volume_handle h, double* d_out);
+int pdwt_volume_estimate_sigma_async(pdwt_volume_handle h, int skip_zeros, double* d_out);
+int pdwt_volume_threshold_bands(pdwt_volume_handle h, int op, const pdwt_real* table, int table_on_device);
+int pdwt_volume_denoise_async(pdwt_volume_handle h, int method, int op, const double* sigma, int skip_zeros);
+int pdwt_volume_adaptive_slots(pdwt_volume_handle h, double** d_stats, double** d_sigma, pdwt_real** d_table);
+int pdwt_volume_select_magnitude_async(pdwt_volume_handle h, long long k, int do_thresh_appcoeffs, pdwt_real* d_threshold,
+                                       unsigned long long* d_kept);
+int pdwt_volume_keep_largest_async(pdwt_volume_handle h, long long k, int do_thresh_appcoeffs);
+int pdwt_volume_sparsify_slots(pdwt_volume_handle h, pdwt_real** d_threshold, unsigned long long** d_kept);
+int pdwt_volume_norms_async(pdwt_volume_handle h, double* d_out2);
+int pdwt_volume_read(pdwt_volume_handle h, void* dst, const void* d_src, long long bytes);
 
 #ifdef __cplusplus
 }

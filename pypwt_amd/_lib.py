@@ -144,6 +144,16 @@ def signatures(real=C.c_float):
         "pdwt_volume_synchronize": (C.c_int, [handle_t]),
         "pdwt_volume_stream": (C.c_void_p, [handle_t]),
         "pdwt_volume_depth_schedule": (C.c_int, [handle_t, C.c_int] + [C.POINTER(C.c_int)] * 3),
+        "pdwt_volume_band_stats_async": (C.c_int, [handle_t, C.c_void_p]),
+        "pdwt_volume_estimate_sigma_async": (C.c_int, [handle_t, C.c_int, C.c_void_p]),
+        "pdwt_volume_threshold_bands": (C.c_int, [handle_t, C.c_int, C.c_void_p, C.c_int]),
+        "pdwt_volume_denoise_async": (C.c_int, [handle_t, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]),
+        "pdwt_volume_adaptive_slots": (C.c_int, [handle_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+        "pdwt_volume_select_magnitude_async": (C.c_int, [handle_t, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
+        "pdwt_volume_keep_largest_async": (C.c_int, [handle_t, C.c_longlong, C.c_int]),
+        "pdwt_volume_sparsify_slots": (C.c_int, [handle_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+        "pdwt_volume_norms_async": (C.c_int, [handle_t, C.c_void_p]),
+        "pdwt_volume_read": (C.c_int, [handle_t, C.c_void_p, C.c_void_p, C.c_longlong]),
     }
 
 

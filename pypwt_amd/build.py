@@ -58,6 +58,7 @@ SOURCES = [
     "launch_swt_invstream.hip",
     "launch_dwt2_split.hip",
     "launch_ops.hip",
+    "launch_volume_ops.hip",
     "launch_nonsep.hip",
     "plan.cpp",
     "volume.cpp",

@@ -204,7 +204,9 @@ hipError_t launch_denoise_table(const BandTable& t, const double* stats, const d
 int select_passes();
 size_t select_state_bytes(int batch);
 size_t select_hist_bytes(int batch);
-hipError_t launch_select_hist(const real_t* band, long long n, int batch, int pass, void* state, unsigned* hist, hipStream_t s);
+// (first: the images start that many values behind `band`; `band` itself stays the aligned base the 16-B groups are counted from)
+hipError_t launch_select_hist(const real_t* band, long long n, int batch, int pass, void* state, unsigned* hist, hipStream_t s,
+                              long long first = 0);
 hipError_t launch_select_walk(long long n, int batch, int pass, int skip_zeros, void* state, unsigned* hist, double* sigma, hipStream_t s);
 // the K-th largest |c| per image over the bands first_band .. of `t` (n values per image in all): the same passes with the
 // histogram sweep over the pieces of `t` and a walk for the rank n - k[image].  d_k: [batch] long long in device memory;
@@ -217,6 +219,18 @@ hipError_t launch_select_walk_rank(int batch, int pass, const long long* d_k, un
                                    real_t* d_threshold, unsigned long long* d_kept, hipStream_t s);
 // x stays iff the bit pattern of |x| >= d_key[image], else +0.0, over the bands first_band .. of `t`, in ONE launch
 hipError_t launch_keep_bands(real_t* arena, const BandTable& t, int first_band, const void* d_key, hipStream_t s);
+// the operators of a volume (volume_ops_kernels.hpp).  t: the swept ranges of all levels, A_L last (with_app = 0 leaves it out);
+// the histogram pass and the keep sweep are the volume's counterparts of launch_select_hist_bands / launch_keep_bands for ONE
+// image, to be used with launch_select_walk_rank(batch = 1).  v: the level plans' slots; stats: [1 + 7 L][2] doubles
+struct VolRangeTable;
+struct VolLevels;
+hipError_t launch_vol_select_hist(const VolRangeTable& t, int with_app, int pass, const long long* d_k, unsigned long long n, const void* state,
+                                  unsigned* hist, hipStream_t s);
+hipError_t launch_vol_keep(const VolRangeTable& t, int with_app, const void* d_key, hipStream_t s);
+hipError_t launch_vol_stats_reduce(const VolLevels& v, double* stats, hipStream_t s);
+hipError_t launch_vol_norms(const double* stats, int nbands, double* out2, hipStream_t s);
+hipError_t launch_vol_table(const VolLevels& v, const double* stats, const double* sigma, int method, double visu, real_t* d_table, hipStream_t s);
+hipError_t launch_vol_expand(const VolLevels& v, const real_t* d_table, hipStream_t s);
 hipError_t launch_circshift(const real_t* in, real_t* out, int batch, int Nr, int Nc, int sr, int sc, hipStream_t s);
 hipError_t launch_copy(const real_t* src, real_t* dst, long long n, hipStream_t s);  // 16-B grid-stride copy (n % 4 == 0)
 hipError_t launch_fill_hash(real_t* x, long long n, uint32_t seed, real_t scale, long long index_offset,

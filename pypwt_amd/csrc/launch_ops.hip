@@ -110,10 +110,10 @@ static long long select_chunk(long long n, int batch) {
     return chunk < 8192 ? 8192 : chunk;
 }
 
-hipError_t launch_select_hist(const real_t* band, long long n, int batch, int pass, void* state, unsigned* hist, hipStream_t s) {
-    if (n < 1 || batch < 1 || batch > 65535 || pass < 0 || pass >= kSelectPasses) return hipErrorInvalidValue;
+hipError_t launch_select_hist(const real_t* band, long long n, int batch, int pass, void* state, unsigned* hist, hipStream_t s, long long first) {
+    if (first < 0 || n < 1 || batch < 1 || batch > 65535 || pass < 0 || pass >= kSelectPasses) return hipErrorInvalidValue;
     const long long chunk = select_chunk(n, batch);
-    hipLaunchKernelGGL(select_hist_kernel, dim3((unsigned)cdivll(n, chunk), batch), dim3(kSelectHistThreads), 0, s, band, n, chunk, pass,
+    hipLaunchKernelGGL(select_hist_kernel, dim3((unsigned)cdivll(n, chunk), batch), dim3(kSelectHistThreads), 0, s, band, first, n, chunk, pass,
                        static_cast<SelectState*>(state), hist);
     return hipGetLastError();
 }

@@ -1,0 +1,56 @@
+// launch_volume_ops.hip -- launchers of the per-sub-band and K-term operators of a volume (gfx950).
+#include "launch.hpp"
+#include "launch_util.hpp"
+// sweep_range and the select's digit logic without a second definition of the kernels of launch_ops.hip
+#define PDWT_INLINE_HELPERS_ONLY
+#include "select_kernels.hpp"
+#undef PDWT_INLINE_HELPERS_ONLY
+#include "volume_ops_kernels.hpp"
+
+namespace pdwt {
+
+static int vol_blocks(const VolRangeTable& t, int with_app) {
+    if (t.nranges < 2 || t.nranges > kVolMaxRanges) return 0;
+    return t.blk[with_app ? t.nranges : t.nranges - 1];
+}
+
+hipError_t launch_vol_select_hist(const VolRangeTable& t, int with_app, int pass, const long long* d_k, unsigned long long n, const void* state,
+                                  unsigned* hist, hipStream_t s) {
+    const int blocks = vol_blocks(t, with_app);
+    if (blocks < 1 || pass < 0 || pass >= kSelectPasses) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(vol_select_hist_kernel, dim3(blocks), dim3(kSelectHistThreads), 0, s, t, pass, d_k, n, static_cast<const SelectState*>(state),
+                       hist);
+    return hipGetLastError();
+}
+
+hipError_t launch_vol_keep(const VolRangeTable& t, int with_app, const void* d_key, hipStream_t s) {
+    const int blocks = vol_blocks(t, with_app);
+    if (blocks < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(vol_keep_kernel, dim3(blocks), dim3(kVolKeepThreads), 0, s, t, static_cast<const select_key_t*>(d_key));
+    return hipGetLastError();
+}
+
+hipError_t launch_vol_stats_reduce(const VolLevels& v, double* stats, hipStream_t s) {
+    if (v.nlevels < 1 || v.nlevels > kVolMaxLevels) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(vol_stats_reduce_kernel, dim3(1 + 7 * v.nlevels), dim3(64), 0, s, v, stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_vol_norms(const double* stats, int nbands, double* out2, hipStream_t s) {
+    hipLaunchKernelGGL(vol_norms_kernel, dim3(1), dim3(64), 0, s, stats, nbands, out2);
+    return hipGetLastError();
+}
+
+hipError_t launch_vol_table(const VolLevels& v, const double* stats, const double* sigma, int method, double visu, real_t* d_table, hipStream_t s) {
+    if (v.nlevels < 1 || v.nlevels > kVolMaxLevels) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(vol_table_kernel, dim3(cdiv(1 + 7 * v.nlevels, 64)), dim3(64), 0, s, v, stats, sigma, method, visu, d_table);
+    return hipGetLastError();
+}
+
+hipError_t launch_vol_expand(const VolLevels& v, const real_t* d_table, hipStream_t s) {
+    if (v.nlevels < 1 || v.nlevels > kVolMaxLevels || v.entry[v.nlevels] < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(vol_expand_kernel, dim3(cdiv(v.entry[v.nlevels], 256)), dim3(256), 0, s, v, d_table);
+    return hipGetLastError();
+}
+
+}  // namespace pdwt

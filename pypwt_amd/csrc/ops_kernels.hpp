@@ -33,6 +33,10 @@
 
 namespace pdwt {
 
+// PDWT_INLINE_HELPERS_ONLY: a second translation unit (launch_volume_ops.hip) takes sweep_range and band_piece without defining the
+// kernels again
+#ifndef PDWT_INLINE_HELPERS_ONLY
+
 template <int OP>
 __device__ __forceinline__ real_t ew_apply(real_t x, real_t b) {
     if (OP == EW_SOFT) return copysign(fmax(fabs(x) - b, real_t(0)), x);
@@ -187,6 +191,8 @@ __global__ void __launch_bounds__(256) norms_final_kernel(const double* __restri
     }
 }
 
+#endif  // !PDWT_INLINE_HELPERS_ONLY
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Operators that tell bands and images apart.  A (band, image) pair is n contiguous values at off[band] + image * n; n is
 // not a multiple of 4 in general (61 x 59 planes, batch 3), so the pairs do not start on 16-B boundaries.  The sweep is cut
@@ -218,6 +224,8 @@ __device__ __forceinline__ void band_piece(const BandTable& t, int blk, int* ban
     *a = lo;
     *e = lo + t.chunk < first + n ? lo + t.chunk : first + n;
 }
+
+#ifndef PDWT_INLINE_HELPERS_ONLY
 
 // partial[2 blk], [2 blk + 1] = sum |x|, sum x^2 over the workgroup's piece (fp64, fixed order: wave shuffles, one LDS step)
 __global__ void __launch_bounds__(256) band_stats_partial_kernel(const real_t* __restrict__ arena, BandTable t, double* __restrict__ partial) {
@@ -384,5 +392,7 @@ __global__ void __launch_bounds__(256) copy_kernel(const real4_t* __restrict__ a
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) b[i] = a[i];
 }
+
+#endif  // !PDWT_INLINE_HELPERS_ONLY
 
 }  // namespace pdwt

@@ -259,11 +259,12 @@ PDWT_DEVICE real_t select_rank_value(select_key_t key) {
 
 constexpr double kSigmaDenominator = 0.6744897501960817;  // the 75 % quantile of the standard normal distribution
 
-#ifndef PDWT_CPU_EMU
+#if !defined(PDWT_CPU_EMU) && !defined(PDWT_INLINE_HELPERS_ONLY)  // (ops_kernels.hpp)
 
-// grid (slices, batch): workgroup (s, i) sweeps [s chunk, min(n, (s + 1) chunk)) of image i of the band (n values per image)
-__global__ void __launch_bounds__(kSelectHistThreads) select_hist_kernel(const real_t* __restrict__ band, long long n, long long chunk, int pass,
-                                                          SelectState* __restrict__ state, unsigned* __restrict__ hist) {
+// grid (slices, batch): workgroup (s, i) sweeps [s chunk, min(n, (s + 1) chunk)) of image i of the band (n values per image); the
+// images start `first` values behind `band`, which is 16-B (fp64: 32-B) aligned whatever `first` is (sweep_range)
+__global__ void __launch_bounds__(kSelectHistThreads) select_hist_kernel(const real_t* __restrict__ band, long long first, long long n, long long chunk,
+                                                          int pass, SelectState* __restrict__ state, unsigned* __restrict__ hist) {
     __shared__ unsigned lh[kSelectLdsWords];
     __shared__ unsigned sh_min, sh_zero;
     const int img = blockIdx.y;
@@ -287,9 +288,9 @@ __global__ void __launch_bounds__(kSelectHistThreads) select_hist_kernel(const r
         sh_zero = 0;
     }
     __syncthreads();
-    const long long a = (long long)img * n + (long long)blockIdx.x * chunk;
+    const long long a = first + (long long)img * n + (long long)blockIdx.x * chunk;
     long long e = a + chunk;
-    if (e > (long long)(img + 1) * n) e = (long long)(img + 1) * n;
+    if (e > first + (long long)(img + 1) * n) e = first + (long long)(img + 1) * n;
     unsigned my_min = kSelectNoDigit, my_zero = 0;
     auto one = [&](real_t x) {
         const select_key_t key = select_key(x);
@@ -419,6 +420,6 @@ __global__ void __launch_bounds__(256) select_walk_rank_kernel(int pass, const l
     }
 }
 
-#endif  // !PDWT_CPU_EMU
+#endif  // !PDWT_CPU_EMU && !PDWT_INLINE_HELPERS_ONLY
 
 }  // namespace pdwt

@@ -1,7 +1,8 @@
 // volume.cpp -- the pdwt_volume_* block of the C ABI (include/pypwt_amd.h): the 3D DWT of a volume as depth passes
 // (launch_dwt3.hip) around one-level batched 2D plans (volume.hpp has the layout).  The 2D side goes through the plans' own
 // entry points -- pdwt_create_batched, pdwt_forward / pdwt_inverse, pdwt_threshold_bands, pdwt_band_stats_async --, so nothing
-// a 1D or 2D plan does is restated here.
+// a 1D or 2D plan does is restated here.  The adaptive and K-term operators pool the slices and levels of a sub-band on the device
+// (volume_ops_kernels.hpp, launch_volume_ops.hip): a volume is ONE image.
 #include "volume.hpp"
 
 #include <math.h>
@@ -165,9 +166,166 @@ int threshold_impl(pdwt_volume* v, int op, real_t beta, int do_app, int normaliz
     return PDWT_OK;
 }
 
+// ---------------------------------------------------------------- operators that pool slices and levels (volume_ops_kernels.hpp)
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// the swept ranges of the K-term operators: per level bands H, V, D and the depth-high half of band A, then A_L; no HIP call
+void build_ranges(pdwt_volume* v) {
+    const int L = v->nlevels;
+    for (int which = 0; which < 2; which++) {
+        VolRangeTable& t = which ? v->rt_keep : v->rt_hist;
+        t.nranges = 0;
+        for (int l = 1; l <= L; l++) {
+            const pdwt_plan* p = v->plans[l - 1];
+            const long long off[4] = {p->bands[0].off, p->bands[1].off, p->bands[2].off, p->bands[3].off};
+            vol_ranges_add_level(t, p->arena, off, v->nz[l], (long long)v->nr[l] * v->nc[l]);
+        }
+        // the pieces of select_hist_bands_kernel (about 1024 of 8192 values at least) and of keep_bands_kernel (2048, 4096): plan.cpp
+        const pdwt_plan* p = v->plans[L - 1];
+        const long long all = vol_ranges_finish(t, p->arena, p->bands[0].off, v->nz[L], (long long)v->nr[L] * v->nc[L], which ? 2048 : 1024,
+                                                which ? 4096 : 8192);
+        v->n_app = (unsigned long long)v->nz[L] * v->nr[L] * v->nc[L];
+        v->n_details = (unsigned long long)all - v->n_app;
+    }
+}
+
+int ensure_ops(pdwt_volume* v) {
+    if (v->ops) return PDWT_OK;
+    const int nb = num_bands(v), L = v->nlevels;
+    VolumeWs* w = new VolumeWs();
+    // (the two sums over all coefficients sit behind the last sub-band's row)
+    const size_t sz_stats = align256((size_t)2 * (nb + 1) * sizeof(double)), sz_sigma = 256, sz_table = align256((size_t)nb * sizeof(real_t)),
+                 sz_state = align256(select_state_bytes(1)), sz_hist = align256(select_hist_bytes(1)), sz_one = 256,
+                 sz_all = sz_stats + sz_sigma + sz_table + sz_state + sz_hist + 4 * sz_one;
+    hipError_t e = hipMalloc(&w->block, sz_all);
+    if (e == hipSuccess) e = hipMemsetAsync(w->block, 0, sz_all, v->stream);  // the walks leave state and histogram zero again
+    if (e == hipSuccess) e = hipHostMalloc(&w->h_stage, 16, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&w->staged, hipEventDisableTiming);
+    int rc = e == hipSuccess ? PDWT_OK : VFAIL(PDWT_ERR_HIP, "workspace of the volume's operators: %s", hipGetErrorString(e));
+    VolLevels& lv = w->levels;
+    lv.nlevels = L;
+    lv.entry[0] = 0;
+    for (int l = 1; l <= L && rc == PDWT_OK; l++) {
+        double* d_stats = nullptr;
+        real_t* d_table = nullptr;
+        rc = pdwt_adaptive_slots(v->plans[l - 1], &d_stats, nullptr, &d_table);
+        lv.half[l - 1] = v->nz[l];
+        lv.n[l - 1] = (long long)v->nz[l] * v->nr[l] * v->nc[l];
+        lv.stats[l - 1] = d_stats;
+        lv.table[l - 1] = d_table;
+        lv.entry[l] = lv.entry[l - 1] + 4 * 2 * v->nz[l];
+    }
+    if (rc != PDWT_OK) {
+        (void)hipGetLastError();
+        if (w->block) (void)hipFree(w->block);
+        if (w->h_stage) (void)hipHostFree(w->h_stage);
+        if (w->staged) (void)hipEventDestroy(w->staged);
+        delete w;
+        return rc;
+    }
+    char* at = static_cast<char*>(w->block);
+    auto take = [&](size_t bytes) {
+        char* here = at;
+        at += bytes;
+        return here;
+    };
+    w->stats = reinterpret_cast<double*>(take(sz_stats));
+    w->norms = w->stats + 2 * nb;
+    w->sigma = reinterpret_cast<double*>(take(sz_sigma));
+    w->table = reinterpret_cast<real_t*>(take(sz_table));
+    w->sel_state = take(sz_state);
+    w->sel_hist = reinterpret_cast<unsigned*>(take(sz_hist));
+    w->sp_k = reinterpret_cast<long long*>(take(sz_one));
+    w->sp_key = take(sz_one);
+    w->sp_threshold = reinterpret_cast<real_t*>(take(sz_one));
+    w->sp_kept = reinterpret_cast<unsigned long long*>(take(sz_one));
+    v->ops = w;
+    return PDWT_OK;
+}
+
+// at most 8 bytes of host data (K, a noise level) to device memory on the volume's stream through the pinned staging buffer; the
+// host waits only if the previous upload has not left the buffer yet (plan.cpp: stage_upload)
+int stage_upload(pdwt_volume* v, void* d_dst, const void* h_src, size_t bytes) {
+    VolumeWs* w = v->ops;
+    HIP_TRY(hipEventSynchronize(w->staged));
+    memcpy(w->h_stage, h_src, bytes);
+    HIP_TRY(hipMemcpyAsync(d_dst, w->h_stage, bytes, hipMemcpyHostToDevice, v->stream));
+    HIP_TRY(hipEventRecord(w->staged, v->stream));
+    return PDWT_OK;
+}
+
+// What every new entry point does first.  The read-only ones take what pdwt_volume_norms takes; the sweeps follow the thresholds.
+int enter_ops(pdwt_volume* v, const char* what, bool sweep) {
+    if (v->state == PDWT_INVERSE)
+        return sweep ? VFAIL(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what)
+                     : VFAIL(PDWT_ERR_STATE, "%s: the coefficients were modified by inverse()", what);
+    PDWT_TRY(mark_current(v));
+    return ensure_ops(v);
+}
+
+// per-slice sums by every level's plan, then one wavefront per sub-band adds up the slices of its depth half
+int band_stats_impl(pdwt_volume* v, double* d_out) {
+    for (pdwt_handle p : v->plans) PDWT_TRY(pdwt_band_stats_async(p, nullptr));
+    HIP_TRY(launch_vol_stats_reduce(v->ops->levels, d_out ? d_out : v->ops->stats, v->stream));
+    return PDWT_OK;
+}
+
+// the exact median of |ddd_1|: the depth-high half of band D of level 1's plan is one contiguous image, `first` values into the arena
+int noise_check(const pdwt_volume* v, const char* what) {
+    const long long n = (long long)v->nz[1] * v->nr[1] * v->nc[1];
+    return n >= (1LL << 32) ? VFAIL(PDWT_ERR_UNSUPPORTED, "%s: the noise band has %lld elements (the histogram bins are 32-bit)", what, n) : PDWT_OK;
+}
+
+int estimate_sigma_impl(pdwt_volume* v, int skip_zeros, double* d_out) {
+    VolumeWs* w = v->ops;
+    const pdwt_plan* p = v->plans[0];
+    const long long n = (long long)v->nz[1] * v->nr[1] * v->nc[1];
+    for (int pass = 0; pass < select_passes(); pass++) {
+        HIP_TRY(launch_select_hist(p->arena, n, 1, pass, w->sel_state, w->sel_hist, v->stream, p->bands[3].off + n));
+        HIP_TRY(launch_select_walk(n, 1, pass, skip_zeros ? 1 : 0, w->sel_state, w->sel_hist, d_out ? d_out : w->sigma, v->stream));
+    }
+    return PDWT_OK;
+}
+
+// every level's sweep with the table its plan holds in its own slot
+int sweep_levels(pdwt_volume* v, int op) {
+    for (int l = 1; l <= v->nlevels; l++) PDWT_TRY(pdwt_threshold_bands(v->plans[l - 1], op, v->ops->levels.table[l - 1], 1));
+    return PDWT_OK;
+}
+
+// N: the swept elements; refused before anything is launched when the 32-bit histogram bins could overflow
+unsigned long long swept(const pdwt_volume* v, int do_app) { return v->n_details + (do_app ? v->n_app : 0); }
+
+int sparsify_check(const pdwt_volume* v, const char* what, long long k, int do_app) {
+    if (k < 0) return VFAIL(PDWT_ERR_ARG, "%s: K = %lld is negative", what, k);
+    if (swept(v, do_app) >= (1ULL << 32))
+        return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: %llu swept elements (the histogram bins are 32-bit)", what, swept(v, do_app));
+    return PDWT_OK;
+}
+
+// the K-th largest |c| over the detail sub-bands (and A_L): the passes of plan.cpp's select_magnitude_impl for ONE image whose
+// pieces lie in every level's arena
+int select_magnitude_impl(pdwt_volume* v, long long k, int do_app, real_t* d_threshold, unsigned long long* d_kept) {
+    VolumeWs* w = v->ops;
+    const unsigned long long n = swept(v, do_app);
+    PDWT_TRY(stage_upload(v, w->sp_k, &k, sizeof(k)));
+    for (int pass = 0; pass < select_passes(); pass++) {
+        HIP_TRY(launch_vol_select_hist(v->rt_hist, do_app ? 1 : 0, pass, w->sp_k, n, w->sel_state, w->sel_hist, v->stream));
+        HIP_TRY(launch_select_walk_rank(1, pass, w->sp_k, n, w->sel_state, w->sel_hist, w->sp_key, d_threshold ? d_threshold : w->sp_threshold,
+                                        d_kept ? d_kept : w->sp_kept, v->stream));
+    }
+    return PDWT_OK;
+}
+
 void destroy(pdwt_volume* v) {
     DeviceGuard guard(v->device);
     if (!v->plans.empty()) (void)hipStreamSynchronize(v->stream);
+    if (VolumeWs* w = v->ops) {
+        if (w->block) (void)hipFree(w->block);
+        if (w->h_stage) (void)hipHostFree(w->h_stage);
+        if (w->staged) (void)hipEventDestroy(w->staged);
+        delete w;
+    }
     for (size_t i = v->plans.size(); i-- > 0;) pdwt_destroy(v->plans[i]);  // plans[0] may own the stream: last
     if (v->image) (void)hipFree(v->image);
     delete v;
@@ -237,6 +395,7 @@ int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char*
         v->nz.push_back(div2(v->nz[l - 1])), v->nr.push_back(div2(v->nr[l - 1])), v->nc.push_back(div2(v->nc[l - 1]));
     }
     v->stream = (hipStream_t)stream;
+    build_ranges(v);
     const size_t bytes = (size_t)Nz * Nr * Nc * sizeof(real_t);
     hipError_t e = hipMalloc((void**)&v->image, bytes);
     if (e != hipSuccess) {
@@ -432,6 +591,119 @@ int pdwt_volume_norms(pdwt_volume_handle v, double out[2]) {
             }
     }
     out[0] = n1, out[1] = n2;
+    return PDWT_OK;
+}
+
+// ---------------------------------------------------------------- NEW: the adaptive and K-term operators on ONE volume
+int pdwt_volume_band_stats_async(pdwt_volume_handle v, double* d_out) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    DeviceGuard guard(v->device);
+    PDWT_TRY(enter_ops(v, "band_stats", false));
+    return band_stats_impl(v, d_out);
+}
+
+int pdwt_volume_norms_async(pdwt_volume_handle v, double* d_out2) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    DeviceGuard guard(v->device);
+    PDWT_TRY(enter_ops(v, "norms", false));
+    PDWT_TRY(band_stats_impl(v, nullptr));
+    HIP_TRY(launch_vol_norms(v->ops->stats, num_bands(v), d_out2 ? d_out2 : v->ops->norms, v->stream));
+    return PDWT_OK;
+}
+
+int pdwt_volume_estimate_sigma_async(pdwt_volume_handle v, int skip_zeros, double* d_out) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    DeviceGuard guard(v->device);
+    PDWT_TRY(noise_check(v, "estimate_sigma"));
+    PDWT_TRY(enter_ops(v, "estimate_sigma", false));
+    return estimate_sigma_impl(v, skip_zeros, d_out);
+}
+
+int pdwt_volume_threshold_bands(pdwt_volume_handle v, int op, const pdwt_real* table, int table_on_device) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (!table) return VFAIL(PDWT_ERR_ARG, "threshold_bands: null table");
+    if (op != EW_SOFT && op != EW_HARD) return VFAIL(PDWT_ERR_ARG, "threshold_bands: op must be 0 (soft) or 1 (hard)");
+    DeviceGuard guard(v->device);
+    PDWT_TRY(enter_ops(v, "threshold_bands", true));
+    if (table_on_device) {
+        HIP_TRY(launch_vol_expand(v->ops->levels, table, v->stream));
+        return sweep_levels(v, op);
+    }
+    // a host table is expanded here and goes through every plan's own staging buffer
+    std::vector<real_t> per;
+    for (int l = 1; l <= v->nlevels; l++) {
+        const int half = v->nz[l], batch = 2 * half;
+        per.resize((size_t)4 * batch);
+        for (int b = 0; b < 4; b++)
+            for (int i = 0; i < batch; i++) {
+                const int num = vol_num_of(l, v->nlevels, b, i, half);
+                per[(size_t)b * batch + i] = num < 0 ? std::numeric_limits<real_t>::quiet_NaN() : table[num];
+            }
+        PDWT_TRY(pdwt_threshold_bands(v->plans[l - 1], op, per.data(), 0));
+    }
+    return PDWT_OK;
+}
+
+int pdwt_volume_denoise_async(pdwt_volume_handle v, int method, int op, const double* sigma, int skip_zeros) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (method != PDWT_DENOISE_BAYES && method != PDWT_DENOISE_VISU) return VFAIL(PDWT_ERR_ARG, "denoise: unknown method %d", method);
+    if (op != EW_SOFT && op != EW_HARD) return VFAIL(PDWT_ERR_ARG, "denoise: op must be 0 (soft) or 1 (hard)");
+    if (!sigma) PDWT_TRY(noise_check(v, "denoise"));
+    DeviceGuard guard(v->device);
+    PDWT_TRY(enter_ops(v, "denoise", true));
+    VolumeWs* w = v->ops;
+    if (sigma) PDWT_TRY(stage_upload(v, w->sigma, sigma, sizeof(double)));
+    else PDWT_TRY(estimate_sigma_impl(v, skip_zeros, nullptr));
+    if (method == PDWT_DENOISE_BAYES) PDWT_TRY(band_stats_impl(v, nullptr));
+    const double visu = sqrt(2.0 * log((double)v->Nz * (double)v->Nr * (double)v->Nc));
+    HIP_TRY(launch_vol_table(w->levels, w->stats, w->sigma, method, visu, w->table, v->stream));
+    HIP_TRY(launch_vol_expand(w->levels, w->table, v->stream));
+    return sweep_levels(v, op);
+}
+
+int pdwt_volume_adaptive_slots(pdwt_volume_handle v, double** d_stats, double** d_sigma, pdwt_real** d_table) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    DeviceGuard guard(v->device);
+    PDWT_TRY(ensure_ops(v));
+    if (d_stats) *d_stats = v->ops->stats;
+    if (d_sigma) *d_sigma = v->ops->sigma;
+    if (d_table) *d_table = v->ops->table;
+    return PDWT_OK;
+}
+
+int pdwt_volume_select_magnitude_async(pdwt_volume_handle v, long long k, int do_thresh_appcoeffs, pdwt_real* d_threshold,
+                                       unsigned long long* d_kept) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    PDWT_TRY(sparsify_check(v, "select_magnitude", k, do_thresh_appcoeffs));
+    DeviceGuard guard(v->device);
+    PDWT_TRY(enter_ops(v, "select_magnitude", false));
+    return select_magnitude_impl(v, k, do_thresh_appcoeffs, d_threshold, d_kept);
+}
+
+int pdwt_volume_keep_largest_async(pdwt_volume_handle v, long long k, int do_thresh_appcoeffs) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    PDWT_TRY(sparsify_check(v, "keep_largest", k, do_thresh_appcoeffs));
+    DeviceGuard guard(v->device);
+    PDWT_TRY(enter_ops(v, "keep_largest", true));
+    PDWT_TRY(select_magnitude_impl(v, k, do_thresh_appcoeffs, nullptr, nullptr));
+    HIP_TRY(launch_vol_keep(v->rt_keep, do_thresh_appcoeffs ? 1 : 0, v->ops->sp_key, v->stream));
+    return PDWT_OK;
+}
+
+int pdwt_volume_sparsify_slots(pdwt_volume_handle v, pdwt_real** d_threshold, unsigned long long** d_kept) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    DeviceGuard guard(v->device);
+    PDWT_TRY(ensure_ops(v));
+    if (d_threshold) *d_threshold = v->ops->sp_threshold;
+    if (d_kept) *d_kept = v->ops->sp_kept;
+    return PDWT_OK;
+}
+
+int pdwt_volume_read(pdwt_volume_handle v, void* dst, const void* d_src, long long bytes) {
+    if (!v || !dst || !d_src || bytes < 0) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_read: bad arguments");
+    DeviceGuard guard(v->device);
+    HIP_TRY(hipMemcpyAsync(dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
     return PDWT_OK;
 }
 

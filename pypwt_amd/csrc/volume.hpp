@@ -20,6 +20,34 @@
 #include <vector>
 
 #include "plan.hpp"
+// the range and level tables of the volume's operators and their index math; the kernels belong to launch_volume_ops.hip
+#define PDWT_INLINE_HELPERS_ONLY
+#include "volume_ops_kernels.hpp"
+#undef PDWT_INLINE_HELPERS_ONLY
+
+namespace pdwt {
+
+// Device workspace of the operators that pool slices and levels into the sub-bands of ONE volume (band_stats, estimate_sigma,
+// threshold_bands, denoise, select_magnitude, keep_largest, norms_async): one block, allocated by the first of them that is called
+// (volume.cpp: ensure_ops), as AdaptiveWs is for a plan.
+struct VolumeWs {
+    void* block = nullptr;
+    double* stats = nullptr;                // [1 + 7 L][2]: sum |c|, sum c^2 of every sub-band
+    double* sigma = nullptr;                // [1]
+    double* norms = nullptr;                // [2]
+    real_t* table = nullptr;                // [1 + 7 L] thresholds of the last denoise
+    void* sel_state = nullptr;              // radix select of one image (select_kernels.hpp)
+    unsigned* sel_hist = nullptr;
+    long long* sp_k = nullptr;              // [1] each: K as the caller gave it, the selected key, the threshold, the kept count
+    void* sp_key = nullptr;
+    real_t* sp_threshold = nullptr;
+    unsigned long long* sp_kept = nullptr;
+    void* h_stage = nullptr;                // pinned: K, or a noise level, on its way to the device
+    hipEvent_t staged = nullptr;
+    VolLevels levels{};                     // the level plans' own slots
+};
+
+}  // namespace pdwt
 
 struct pdwt_volume {
     int device = 0;
@@ -33,4 +61,8 @@ struct pdwt_volume {
     std::vector<int> seg_fwd, seg_inv;  // [l - 1]: steps per depth segment of level l's depth passes
     std::vector<int> width;             // [l - 1]: columns per thread of level l's depth passes
     pdwt::FilterBank dec{}, rec{};
+    // the swept ranges of the K-term operators, fixed with the layout: pieces of the histogram passes (1024 threads) and of the keep sweep
+    pdwt::VolRangeTable rt_hist{}, rt_keep{};
+    unsigned long long n_details = 0, n_app = 0;  // elements of the 7 L detail sub-bands, of A_L
+    pdwt::VolumeWs* ops = nullptr;
 };

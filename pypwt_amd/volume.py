@@ -5,6 +5,8 @@ The reference stops at two dimensions ("3D is not handled at the moment", pdwt/R
 rest of the library (pywt's "periodization").  ctypes binding only.
 
     W = Wavelets3D(vol, "db2", 3); W.forward(); W.soft_threshold(10); W.inverse(); W.coeffs; W.image
+    W.forward(); W.denoise("BayesShrink"); W.inverse()        # the threshold of every sub-band from the data, on the device
+    W.forward(); W.keep_largest(fraction=0.05); W.inverse()   # best K-term approximation
 """
 import ctypes as C
 
@@ -208,6 +210,180 @@ class Wavelets3D(object):
 
     def norm2sq(self):
         return self.norms()[1]
+
+    # ---- operators that choose the threshold, or the sparsity, from the data: `Wavelets`' methods with the volume as ONE image
+    _DENOISE_METHODS = {"bayesshrink": 0, "visushrink": 1}
+    _THRESHOLD_MODES = {"soft": 0, "hard": 1}
+
+    @staticmethod
+    def _choice(table, name, what):
+        try:
+            return table[str(name).lower()]
+        except KeyError:
+            raise ValueError("unknown %s %r (expected one of %s)" % (what, name, ", ".join(sorted(table))))
+
+    def _refused(self, rc):
+        """As for `soft_threshold` after inverse(): a warning, nothing done."""
+        if rc == _lib.ERR_STATE:
+            print("Warning: Wavelets3D(): " + _lib.last_error(self._lib))
+            return True
+        self._check(rc)
+        return False
+
+    def _adaptive_slots(self):
+        st, sg, tb = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self._lib.pdwt_volume_adaptive_slots(self._h, C.byref(st), C.byref(sg), C.byref(tb)), "pdwt_volume_adaptive_slots")
+        return st.value, sg.value, tb.value
+
+    def _sparsify_slots(self):
+        th, kp = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.pdwt_volume_sparsify_slots(self._h, C.byref(th), C.byref(kp)), "pdwt_volume_sparsify_slots")
+        return th.value, kp.value
+
+    def _view(self, ptr, shape, dtype):
+        return DeviceArray(self, ptr, shape, dtype, self._stream())
+
+    def _out(self, out, count, which):
+        """(argument for the C call, view to return) of an optional caller-owned float64 device array."""
+        if out is None:
+            return C.c_void_p(None), None
+        dev = _device_array(out, np.float64)
+        if dev is None or int(np.prod(dev[1])) < count:
+            raise ValueError("%s: `out` must be a device array of %d float64" % (which, count))
+        return C.c_void_p(dev[0]), out
+
+    def _read(self, addr, shape, dtype):
+        """Device memory copied to the host on the volume's stream (waits for it)."""
+        host = np.zeros(shape, dtype=dtype)
+        self._check(self._lib.pdwt_volume_read(self._h, host.ctypes.data_as(C.c_void_p), C.c_void_p(int(addr)), host.nbytes), "pdwt_volume_read")
+        return host
+
+    @staticmethod
+    def _addr(view):
+        return int(view.__cuda_array_interface__["data"][0])
+
+    def band_stats(self, out=None):
+        """(sum |c|, sum c^2) of every sub-band as float64 ON THE DEVICE: a (nbands, 2) device array -- ``out`` if given, else a
+        view of the volume's own slot.  Slices and levels are pooled on the device; two calls give the same bits."""
+        arg, view = self._out(out, 2 * self.nbands, "band_stats")
+        self._check(self._lib.pdwt_volume_band_stats_async(self._h, arg), "band_stats")
+        return view if view is not None else self._view(self._adaptive_slots()[0], (self.nbands, 2), np.float64)
+
+    def read_band_stats(self, view=None):
+        """What ``band_stats`` left on the device, copied to the host (waits for the volume's stream): (nbands, 2) float64."""
+        return self._read(self._adaptive_slots()[0] if view is None else self._addr(view), (self.nbands, 2), np.float64)
+
+    def estimate_sigma(self, skip_zeros=True, out=None):
+        """The noise level sigma = median(|ddd_1|) / 0.6745 over the WHOLE finest 'ddd' sub-band (``num`` 7; the rule of
+        skimage.restoration.denoise_wavelet for n-D data), as float64 ON THE DEVICE: a (1,) device array.  The median is exact;
+        ``skip_zeros`` (default, as skimage does) leaves exact zeros out of it."""
+        arg, view = self._out(out, 1, "estimate_sigma")
+        self._check(self._lib.pdwt_volume_estimate_sigma_async(self._h, 1 if skip_zeros else 0, arg), "estimate_sigma")
+        return view if view is not None else self._view(self._adaptive_slots()[1], (1,), np.float64)
+
+    def read_sigma(self, view=None):
+        """What ``estimate_sigma`` (or ``denoise``) left on the device, copied to the host: (1,) float64."""
+        return self._read(self._adaptive_slots()[1] if view is None else self._addr(view), (1,), np.float64)
+
+    def threshold_bands(self, betas, mode="soft"):
+        """Soft or hard threshold with a threshold of its own per sub-band: ``betas`` is a (nbands,) array of the instance's dtype
+        -- a numpy array or any device-array holder ``set_coeff`` accepts.  A NaN entry leaves that sub-band untouched (entry 0 is
+        the approximation A_L)."""
+        op = self._choice(self._THRESHOLD_MODES, mode, "mode")
+        dev = _device_array(betas, self._dtype)
+        if dev is not None:
+            if int(np.prod(dev[1])) != self.nbands:
+                raise ValueError("threshold_bands: expected %d thresholds, got %d" % (self.nbands, int(np.prod(dev[1]))))
+            self._order_producer(dev)
+            self._refused(self._lib.pdwt_volume_threshold_bands(self._h, op, C.c_void_p(dev[0]), 1))
+            return
+        t = np.ascontiguousarray(np.asarray(betas, dtype=self._dtype))
+        if t.shape != (self.nbands,):
+            raise ValueError("threshold_bands: expected thresholds of shape (%d,), got %s" % (self.nbands, str(t.shape)))
+        self._refused(self._lib.pdwt_volume_threshold_bands(self._h, op, _ptr(t), 0))
+
+    def denoise(self, method="BayesShrink", sigma=None, mode="soft", skip_zeros=True):
+        """Adaptive wavelet shrinkage of the current coefficients (run ``forward`` before and ``inverse`` after it).
+        ``method``: "BayesShrink" (a threshold per detail sub-band) or "VisuShrink" (sigma sqrt(2 ln(Nz Nr Nc))); ``sigma``: the
+        noise level, None = ``estimate_sigma``; ``mode``: "soft" or "hard".  Nothing goes through the host; ``last_thresholds``
+        shows what was applied."""
+        m = self._choice(self._DENOISE_METHODS, method, "method")
+        op = self._choice(self._THRESHOLD_MODES, mode, "mode")
+        arg = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(np.atleast_1d(np.asarray(sigma, dtype=np.float64)))
+            if sg.shape != (1,):
+                raise ValueError("denoise: sigma must be one number (a volume is one image)")
+            arg = sg.ctypes.data_as(C.POINTER(C.c_double))
+        self._refused(self._lib.pdwt_volume_denoise_async(self._h, m, op, arg, 1 if skip_zeros else 0))
+
+    def last_thresholds(self):
+        """(sigma, thresholds) of the last ``denoise``, copied to the host (waits for the volume's stream): sigma is (1,) float64,
+        thresholds (nbands,) of the instance's dtype with NaN at index 0 (the approximation is left alone)."""
+        _, sg, tb = self._adaptive_slots()
+        return self._read(sg, (1,), np.float64), self._read(tb, (self.nbands,), self._dtype)
+
+    def _sparsify_count(self, do_threshold_appcoeffs):
+        """N: the elements of the swept sub-bands (the 7 L detail sub-bands, and A_L when asked for), from the band shapes."""
+        return sum(int(np.prod(shp)) for shp in self._shapes[0 if do_threshold_appcoeffs else 1:])
+
+    def _sparsify_k(self, what, k, fraction, do_threshold_appcoeffs):
+        expected = "%s: expected exactly one of k (an int >= 0) and fraction (a number in [0, 1])" % what
+        if (k is None) == (fraction is None):
+            raise ValueError(expected)
+        if fraction is not None:
+            try:
+                f = float(fraction)
+            except (TypeError, ValueError):
+                raise ValueError(expected + ", got fraction=%r" % (fraction,))
+            if not 0.0 <= f <= 1.0:  # a NaN fails both comparisons
+                raise ValueError(expected + ", got fraction=%r" % (fraction,))
+            return int(round(f * self._sparsify_count(do_threshold_appcoeffs)))
+        try:
+            arr = np.asarray(k)
+            if arr.dtype.kind not in "iu" or arr.size != 1 or int(arr.reshape(-1)[0]) < 0 or int(arr.reshape(-1)[0]) > np.iinfo(np.int64).max:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(expected + ", got k=%r" % (k,))
+        return int(arr.reshape(-1)[0])
+
+    def select_magnitude(self, k=None, fraction=None, do_threshold_appcoeffs=0):
+        """The K-th largest ``|c|`` over the detail sub-bands of all levels (and A_L with ``do_threshold_appcoeffs``), EXACT, and
+        how many elements are at least that large: ``(threshold, kept)`` as device views of the volume's slots, (1,) of the
+        instance's dtype and (1,) uint64.  ``fraction``: K = round(fraction * N).  Read-only; ``last_sparsify`` copies the pair to
+        the host.  K = 0 gives (+inf, 0), K >= N gives (0, N)."""
+        kk = self._sparsify_k("select_magnitude", k, fraction, do_threshold_appcoeffs)
+        self._check(self._lib.pdwt_volume_select_magnitude_async(self._h, kk, 1 if do_threshold_appcoeffs else 0, None, None), "select_magnitude")
+        th, kp = self._sparsify_slots()
+        return self._view(th, (1,), self._dtype), self._view(kp, (1,), np.uint64)
+
+    def keep_largest(self, k=None, fraction=None, do_threshold_appcoeffs=0):
+        """Best K-term approximation of the volume: keep, bit for bit, the K coefficients of largest magnitude (ties with the K-th
+        all survive; NaNs count as larger than +inf) and set the rest to +0.0 -- the select above and one sweep over all levels,
+        nothing through the host.  After ``inverse()`` it warns and does nothing, like every threshold."""
+        kk = self._sparsify_k("keep_largest", k, fraction, do_threshold_appcoeffs)
+        self._refused(self._lib.pdwt_volume_keep_largest_async(self._h, kk, 1 if do_threshold_appcoeffs else 0))
+
+    def last_sparsify(self):
+        """(threshold, kept) of the last ``select_magnitude`` / ``keep_largest``, copied to the host (waits for the volume's
+        stream): (1,) of the instance's dtype and (1,) uint64."""
+        th, kp = self._sparsify_slots()
+        return self._read(th, (1,), self._dtype), self._read(kp, (1,), np.uint64)
+
+    def norms_device(self, out=None):
+        """(sum |c|, sum c^2) over all coefficients as two float64 ON THE DEVICE, enqueued and not waited for (``norms`` blocks):
+        the fixed-order sum of the ``band_stats`` rows.  Returns ``out`` if given, else a view of the volume's own slot."""
+        arg, view = self._out(out, 2, "norms_device")
+        self._check(self._lib.pdwt_volume_norms_async(self._h, arg), "norms_device")
+        if view is not None:
+            return view
+        return self._view(self._adaptive_slots()[0] + 2 * self.nbands * 8, (2,), np.float64)
+
+    def read_norms(self, view=None):
+        """The two float64 a ``norms_device`` call left on the device, copied to the host (waits for the volume's stream)."""
+        addr = self._adaptive_slots()[0] + 2 * self.nbands * 8 if view is None else self._addr(view)
+        res = self._read(addr, (2,), np.float64)
+        return float(res[0]), float(res[1])
 
     # ---- device views
     def _stream(self):

@@ -11,6 +11,15 @@ Beside them the yardstick of the same run: the flat copy of the same bytes (pdwt
 level-1 slice stack) and the share of it that this plan's own level-1 2D kernel reaches (pdwt_time_level).  Gsamples/s and
 the bytes moved per sample are computed from the shapes.
 
+--ops: the operators on the coefficients of a volume (256^3 and 512^3 db4, three levels), each timed twice in the same call: the
+global soft threshold and forward + soft + inverse as yardsticks, then band_stats, estimate_sigma, denoise, select_magnitude,
+forward + keep_largest (keep_largest needs fresh coefficients every time; the forward of the same run is the line above it) and
+forward + denoise + inverse.  Beside the times the rate at which the coefficients are READ: all 1 + 7 L sub-bands once for the
+sweeps and the sums, the finest 'ddd' sub-band once per pass for estimate_sigma, the 7 L detail sub-bands once per pass for
+select_magnitude; the keep sweep's own time is (forward + keep_largest) - forward - select_magnitude.
+
+    python tools/volbench.py --ops                 > profiles/volume_opsbench.txt
+
 --profile: a short run of ONE case with one level (so that every kernel name in the trace belongs to level 1) plus the copy and
 the 2D level of the same bytes, for rocprofv3; --summarize reads the kernel trace of such a run and reports, per depth kernel,
 its share of the copy next to the share the 2D level-1 kernel reaches.
@@ -132,6 +141,79 @@ def run_bench(args):
         sys.stdout.flush()
 
 
+OPS_CASES = [("256^3 db4", (256, 256, 256), "db4", 3), ("512^3 db4", (512, 512, 512), "db4", 3)]
+
+
+def run_ops(args):
+    ev = Events()
+    passes = 3  # fp32 keys: 11 + 10 + 10 bits
+    print("# volbench --ops: operators on the coefficients of a volume, fp32, %d calls per timing after %d warm-up calls; every line timed twice"
+          % (args.reps, args.warmup))
+    print("# GB/s: coefficient bytes READ per call / the faster time (see the module docstring for what each operator reads)")
+    print("# %-11s %-22s %10s %10s %10s" % ("case", "operator", "ms (1st)", "ms (2nd)", "GB/s read"))
+    for k, (name, shape, wname, levels) in enumerate(OPS_CASES):
+        if args.case is not None and k != args.case:
+            continue
+        W = make_volume(shape, wname, levels)
+        W.forward()
+        lib, h = W._lib, W._h
+        sizes = [int(np.prod(W.band_shape(num))) for num in range(W.nbands)]
+        n_all, n_det, n_noise = sum(sizes), sum(sizes[1:]), sizes[7]
+        kk = n_det // 10
+
+        def ok(rc):
+            assert rc == 0, rc
+
+        def soft():
+            ok(lib.pdwt_volume_soft_threshold(h, 10.0, 0, 0))
+
+        def fwd():
+            ok(lib.pdwt_volume_forward(h))
+
+        def inv():
+            ok(lib.pdwt_volume_inverse(h))
+
+        def fwd_soft_inv():
+            fwd(), soft(), inv()
+
+        def stats():
+            ok(lib.pdwt_volume_band_stats_async(h, None))
+
+        def sigma():
+            ok(lib.pdwt_volume_estimate_sigma_async(h, 1, None))
+
+        def denoise():
+            ok(lib.pdwt_volume_denoise_async(h, 0, 0, None, 1))
+
+        def select():
+            ok(lib.pdwt_volume_select_magnitude_async(h, kk, 0, None, None))
+
+        def fwd_keep():
+            fwd()
+            ok(lib.pdwt_volume_keep_largest_async(h, kk, 0))
+
+        def fwd_denoise_inv():
+            fwd(), denoise(), inv()
+
+        rows = [("soft_threshold", soft, 4 * n_all), ("fwd+soft+inv", fwd_soft_inv, 0), ("forward", fwd, 0), ("band_stats", stats, 4 * n_all),
+                ("estimate_sigma", sigma, 4 * passes * n_noise), ("select_magnitude K=N/10", select, 4 * passes * n_det),
+                ("fwd+keep_largest K=N/10", fwd_keep, 0), ("denoise BayesShrink", denoise, 4 * (passes * n_noise + 2 * n_all)),
+                ("fwd+denoise+inv", fwd_denoise_inv, 0)]
+        got = {}
+        for oname, fn, nbytes in rows:
+            if oname in ("band_stats", "estimate_sigma", "select_magnitude K=N/10", "denoise BayesShrink", "soft_threshold"):
+                fwd()  # dense coefficients under every operator that is timed on its own
+            t = [ev.time(W._stream(), fn, args.reps, args.warmup) for _ in range(2)]
+            got[oname] = min(t)
+            rate = "%10.0f" % (nbytes / (min(t) * 1e6)) if nbytes else "%10s" % "-"
+            print("  %-11s %-22s %10.4f %10.4f %s" % (name, oname, t[0], t[1], rate))
+        keep = got["fwd+keep_largest K=N/10"] - got["forward"] - got["select_magnitude K=N/10"]
+        print("  %-11s keep sweep alone: %.4f ms = %.0f GB/s read (and as much written where a value falls); N = %d, all coefficients %d"
+              % (name, keep, 4 * n_det / (keep * 1e6) if keep > 0 else float("nan"), n_det, n_all))
+        sys.stdout.flush()
+        W.cleanup()
+
+
 def run_profile(args):
     name, shape, wname, _ = CASES[args.case]
     W = make_volume(shape, wname, 1)
@@ -176,6 +258,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--case", type=int, default=None)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--ops", action="store_true")
     ap.add_argument("--summarize", default=None)
     ap.add_argument("--list", action="store_true")
     args = ap.parse_args()
@@ -187,6 +270,8 @@ def main():
         run_summarize(args)
     elif args.profile:
         run_profile(args)
+    elif args.ops:
+        run_ops(args)
     else:
         run_bench(args)
 
