@@ -115,6 +115,21 @@ long long pdwt_copy_capacity(pdwt_handle h); /* the largest `elems` pdwt_time_co
  *                    slower than two launches on MI355X, kept for tests and re-measurement) */
 int pdwt_set_tuning(const char* key, int value);
 
+/* Test hooks of a volume (tests/test_gpu_volume_taps.py).  Custom filter banks on volumes are NOT part of the product: these two
+ * exist so that every depth-kernel instantiation can be run with a bank whose every tap counts, at every segment length.
+ *
+ * The first replaces the four filters of the volume's depth passes and of every level's 2D plan (the plans' own
+ * set_filters_forward / set_filters_inverse).  hlen must be the length the volume was created with: the level count, the access
+ * widths and the depth segments stay as created.  Image, coefficients and state are left alone.  PDWT_ERR_ARG for another length or
+ * a null filter; nothing is changed then. */
+int pdwt_volume_set_filters(pdwt_volume_handle h, int hlen, const pdwt_real* dec_lo, const pdwt_real* dec_hi, const pdwt_real* rec_lo,
+                            const pdwt_real* rec_hi);
+/* The second overrides the steps a workgroup walks per depth segment of level `level` (1 .. nlevels), forward and inverse: 0 restores
+ * what the chooser picked when the volume was created, any other value must lie in [1, steps of a whole walk] -- div2(depth)
+ * forward, the synthesis' step count inverse --, else PDWT_ERR_ARG and nothing is changed.  pdwt_volume_depth_schedule reports
+ * what is in force. */
+int pdwt_volume_set_depth_segments(pdwt_volume_handle h, int level, int seg_fwd, int seg_inv);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,8 @@ def signatures(real=C.c_float):
         "pdwt_volume_sparsify_slots": (C.c_int, [handle_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
         "pdwt_volume_norms_async": (C.c_int, [handle_t, C.c_void_p]),
         "pdwt_volume_read": (C.c_int, [handle_t, C.c_void_p, C.c_void_p, C.c_longlong]),
+        "pdwt_volume_set_filters": (C.c_int, [handle_t, C.c_int, realp, realp, realp, realp]),
+        "pdwt_volume_set_depth_segments": (C.c_int, [handle_t, C.c_int, C.c_int, C.c_int]),
     }
 
 

@@ -74,6 +74,11 @@ typedef float4 real4_t;
 #endif
 #endif
 
+// every even filter length of the built-in table gets its own fully unrolled instantiation (here, not in launch.hpp: the host
+// emulation of tests/cpu_emu takes its lengths from the same list and cannot include the HIP runtime)
+#define PDWT_EVEN_HLENS(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) \
+    X(28) X(30) X(32) X(34) X(36) X(38) X(40)
+
 namespace pdwt {
 
 constexpr int kMaxTaps = 40;  // same limit as the reference (pdwt/src/common.h:15)

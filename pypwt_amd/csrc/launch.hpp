@@ -8,10 +8,6 @@
 
 namespace pdwt {
 
-// every even filter length of the built-in table gets its own fully unrolled instantiation
-#define PDWT_EVEN_HLENS(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) \
-    X(28) X(30) X(32) X(34) X(36) X(38) X(40)
-
 // element-wise operator codes of launch_ew
 enum EwOp { EW_SOFT = 0, EW_HARD = 1, EW_LINF = 2, EW_SCALE = 3 };
 

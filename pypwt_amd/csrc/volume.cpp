@@ -419,6 +419,7 @@ int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char*
         v->seg_fwd.push_back(dwt3_depth_seg(v->nz[l - 1], P, v->hlen, width, false, dwt3_depth_slots(v->hlen, width, false)));
         v->seg_inv.push_back(dwt3_depth_seg(v->nz[l - 1], P, v->hlen, width, true, dwt3_depth_slots(v->hlen, width, true)));
     }
+    v->seg_fwd_chosen = v->seg_fwd, v->seg_inv_chosen = v->seg_inv;
     *out = v;
     return PDWT_OK;
 }
@@ -722,6 +723,39 @@ int pdwt_volume_depth_schedule(pdwt_volume_handle v, int level, int* width, int*
     if (width) *width = v->width[level - 1];
     if (seg_fwd) *seg_fwd = v->seg_fwd[level - 1];
     if (seg_inv) *seg_inv = v->seg_inv[level - 1];
+    return PDWT_OK;
+}
+
+// ---------------------------------------------------------------- test hooks (include/pypwt_amd_bench.h)
+int pdwt_volume_set_filters(pdwt_volume_handle v, int hlen, const pdwt_real* dec_lo, const pdwt_real* dec_hi, const pdwt_real* rec_lo,
+                            const pdwt_real* rec_hi) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (!dec_lo || !dec_hi || !rec_lo || !rec_hi) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_set_filters: null filter");
+    if (hlen != v->hlen)
+        return VFAIL(PDWT_ERR_ARG, "pdwt_volume_set_filters: %d taps, the volume was created with %d (the schedule is not rebuilt)", hlen, v->hlen);
+    DeviceGuard guard(v->device);
+    // the level plans first: a plan that refuses leaves the volume's own bank as it was
+    for (pdwt_handle p : v->plans) {
+        PDWT_TRY(pdwt_set_filters_forward(p, nullptr, (unsigned)hlen, dec_lo, dec_hi, nullptr, nullptr));
+        PDWT_TRY(pdwt_set_filters_inverse(p, rec_lo, rec_hi, nullptr, nullptr));
+    }
+    for (int i = 0; i < kMaxTaps; i++) {
+        const bool in = i < hlen;
+        v->dec.lo[i] = in ? dec_lo[i] : 0, v->dec.hi[i] = in ? dec_hi[i] : 0;
+        v->rec.lo[i] = in ? rec_lo[i] : 0, v->rec.hi[i] = in ? rec_hi[i] : 0;
+    }
+    return PDWT_OK;
+}
+
+int pdwt_volume_set_depth_segments(pdwt_volume_handle v, int level, int seg_fwd, int seg_inv) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (level < 1 || level > v->nlevels) return VFAIL(PDWT_ERR_ARG, "level %d out of range (1 .. %d)", level, v->nlevels);
+    const int steps_fwd = dwt3_depth_steps(v->nz[level - 1], v->hlen, false), steps_inv = dwt3_depth_steps(v->nz[level - 1], v->hlen, true);
+    if (seg_fwd < 0 || seg_fwd > steps_fwd || seg_inv < 0 || seg_inv > steps_inv)
+        return VFAIL(PDWT_ERR_ARG, "pdwt_volume_set_depth_segments: (%d, %d) steps per segment, level %d walks (%d, %d) steps", seg_fwd, seg_inv,
+                     level, steps_fwd, steps_inv);
+    v->seg_fwd[level - 1] = seg_fwd ? seg_fwd : v->seg_fwd_chosen[level - 1];
+    v->seg_inv[level - 1] = seg_inv ? seg_inv : v->seg_inv_chosen[level - 1];
     return PDWT_OK;
 }
 

@@ -59,6 +59,7 @@ struct pdwt_volume {
     std::vector<pdwt_handle> plans;     // [l - 1]: the batched 2D plan of level l; plans[0] owns the stream unless the caller gave one
     std::vector<int> nz, nr, nc;        // [l]: sizes of A_l, [0] = the image
     std::vector<int> seg_fwd, seg_inv;  // [l - 1]: steps per depth segment of level l's depth passes
+    std::vector<int> seg_fwd_chosen, seg_inv_chosen;  // [l - 1]: the chooser's values (pdwt_volume_set_depth_segments restores them)
     std::vector<int> width;             // [l - 1]: columns per thread of level l's depth passes
     pdwt::FilterBank dec{}, rec{};
     // the swept ranges of the K-term operators, fixed with the layout: pieces of the histogram passes (1024 threads) and of the keep sweep

@@ -120,6 +120,20 @@ class Wavelets3D(object):
         self._check(self._lib.pdwt_volume_depth_schedule(self._h, int(level), *[C.byref(x) for x in v]), "depth_schedule")
         return tuple(x.value for x in v)
 
+    def _set_filters(self, filt):
+        """Test plumbing (pdwt_volume_set_filters): `filt` = (hlen, dec_lo, dec_hi, rec_lo, rec_hi) replaces the bank of the depth
+        passes and of every level's 2D plan; hlen must be the volume's own.  Custom banks on volumes are not part of the product."""
+        taps = [np.ascontiguousarray(t, dtype=self._dtype) for t in filt[1:5]]
+        if any(t.shape != (int(filt[0]),) for t in taps):
+            raise ValueError("Wavelets3D._set_filters: four filters of %d taps expected" % int(filt[0]))
+        rp = C.POINTER(self._lib.pdwt_real)
+        self._check(self._lib.pdwt_volume_set_filters(self._h, int(filt[0]), *[C.cast(t.ctypes.data, rp) for t in taps]), "_set_filters")
+
+    def _set_depth_segments(self, level, seg_fwd, seg_inv):
+        """Test plumbing (pdwt_volume_set_depth_segments): steps per depth segment of `level`, forward and inverse; 0 restores the
+        chooser's value."""
+        self._check(self._lib.pdwt_volume_set_depth_segments(self._h, int(level), int(seg_fwd), int(seg_inv)), "_set_depth_segments")
+
     def band_shape(self, num):
         return self._shapes[num]
 

@@ -62,6 +62,7 @@ EMU_API int emu_axis_seg(int Nz, long long P, int hlen, int width, int inverse, 
 // a combination that is not built
 EMU_API int emu_axis_run(const real_t* in, real_t* out, int Nz, long long P, int hlen, const real_t* lo, const real_t* hi, int seg,
                          int width, int inverse) {
+    if (hlen < 1 || hlen > kMaxTaps) return -1;
     Dwt3Args a;
     memset(&a, 0, sizeof(a));
     a.in = in;
@@ -71,13 +72,10 @@ EMU_API int emu_axis_run(const real_t* in, real_t* out, int Nz, long long P, int
     a.P = P;
     a.seg = seg;
     for (int i = 0; i < hlen; i++) a.fb.lo[i] = lo[i], a.fb.hi[i] = hi[i];
-    switch (hlen) {
-        case 2: return run_width<2>(a, width, inverse != 0);
-        case 4: return run_width<4>(a, width, inverse != 0);
-        case 8: return run_width<8>(a, width, inverse != 0);
-        case 16: return run_width<16>(a, width, inverse != 0);
-        case 18: return run_width<18>(a, width, inverse != 0);
-        case 40: return run_width<40>(a, width, inverse != 0);
+    switch (hlen) {  // every even length the launchers instantiate: one list (kernels_common.hpp)
+#define X(h) case h: return run_width<h>(a, width, inverse != 0);
+        PDWT_EVEN_HLENS(X)
+#undef X
     }
     return -1;
 }

@@ -11,11 +11,16 @@ the fp32 oracle in summation order and fma contraction only).  A kernel is compa
 one fp32 ulp of the band's maximum.
 
 K = 4.  The largest err / noise measured on the MI355X is 2.50 (the inverse strip kernels; every family and direction:
-profiles/taps_parity.txt), so 4 holds.  (K may be raised to twice the largest ratio a correct kernel needs, never beyond 16;
-tests/test_tap_banks_cpu.py demands that zeroing any single tap still moves the oracle by 1000 x the tolerance, whatever K is.)"""
+profiles/taps_parity.txt); through the depth kernels of a volume it is 2.00 (every even length 4-40, both widths, both directions, forced
+depth segments: profiles/volume_taps_parity.txt).  So 4 holds.  (K may be raised to twice the largest ratio a correct kernel needs, never beyond 16;
+tests/test_tap_banks_cpu.py and tests/test_volume_taps_cpu.py demand that zeroing any single tap still moves the oracle by 1000 x the
+tolerance, whatever K is.)
+
+The volume_* helpers below are the same rule for one level of a volume: the composition of tests/volume_ref.py in the place of the oracle."""
 import numpy as np
 
 from oracle import oracle
+import volume_ref
 
 K = 4.0
 K_MAX = 16.0
@@ -83,3 +88,40 @@ def assert_inverse(w, ref, levels, filt, cap, tag, ndim=2, do_swt=0):
     want, (tol, noise) = inverse_reference(ref, got.shape if got.ndim == 2 else (1, got.size), levels, filt, ndim=ndim, do_swt=do_swt)
     err = float(np.abs(got.reshape(want.shape).astype(np.float64) - want).max())
     assert err <= min(tol, cap * max(float(np.abs(want).max()), 1.0)), (tag, err, tol, noise)
+
+
+# ---- volumes: one level of Wavelets3D (tests/test_volume_taps_cpu.py, tests/test_gpu_volume_taps.py) -----------------------------
+
+def volume_shapes(n):
+    """The two volumes an n-tap depth kernel is run on.  A: an odd depth of at least n slices, planes of 96 samples (whole 16-B groups:
+    the wide access); B: a depth below the filter length (the source counter wraps up to six times per window at 40 taps), planes
+    of 99 samples (one column per lane)."""
+    return (n + 7, 8, 12), (3 if n < 8 else 7, 9, 11)
+
+
+def volume_input(shape, seed):
+    return oracle.hash_input(shape, seed)
+
+
+def volume_forward_reference(x, filt, k=None, depth_filt=None):
+    """One level of the f64acc composition (tests/volume_ref.py) with `filt` on all three axes: its eight bands in `num` order, and
+    per band (tolerance, noise) with noise = max |fp32 composition - f64acc composition|."""
+    k = K if k is None else k
+    ref = volume_ref.forward(x, None, 1, True, filt=filt, depth_filt=depth_filt)
+    f32 = volume_ref.forward(x, None, 1, False, filt=filt, depth_filt=depth_filt)
+    return ref, [_tol(r, f, k) for r, f in zip(ref, f32)]
+
+
+def volume_inverse_reference(bands, shape, filt, k=None, depth_filt=None):
+    """The f64acc composition's synthesis of `bands` (fp32 arrays, e.g. volume_forward_reference's), and its (tolerance, noise)."""
+    k = K if k is None else k
+    ref = volume_ref.inverse(bands, shape, None, 1, True, filt=filt, depth_filt=depth_filt)
+    f32 = volume_ref.inverse(bands, shape, None, 1, False, filt=filt, depth_filt=depth_filt)
+    return ref, _tol(ref, f32, k)
+
+
+def depth_tap_factor(x, filt, which, j, ref, tols):
+    """Zeroing tap j of dec_lo (which = 1) or dec_hi (2) in the DEPTH step alone moves the f64acc composition by this many
+    tolerances in the band it moves most; ref, tols: volume_forward_reference(x, filt)."""
+    got = volume_ref.forward(x, None, 1, True, filt=filt, depth_filt=without_tap(filt, which, j))
+    return max(float(np.abs(g.astype(np.float64) - r).max()) / tol for g, r, (tol, _) in zip(got, ref, tols))

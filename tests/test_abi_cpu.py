@@ -30,7 +30,8 @@ def header_functions(which=("pypwt_amd.h", "pypwt_amd_bench.h")):
 
 
 BENCH_ONLY = {"pdwt_fill_image_hash", "pdwt_enable_kernel_timing", "pdwt_kernel_times", "pdwt_reset_kernel_times", "pdwt_time_level",
-              "pdwt_time_copy", "pdwt_copy_capacity", "pdwt_schedule_string", "pdwt_set_tuning", "pdwt_kernel_families"}
+              "pdwt_time_copy", "pdwt_copy_capacity", "pdwt_schedule_string", "pdwt_set_tuning", "pdwt_kernel_families",
+              "pdwt_volume_set_filters", "pdwt_volume_set_depth_segments"}
 
 
 def test_the_contract_header_holds_no_measurement_hook():

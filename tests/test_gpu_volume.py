@@ -380,3 +380,68 @@ def test_fp64_forward_inverse_round_trip(classes, case):
     W.soft_threshold(17.25, 1, 1)
     for num, (g, w) in enumerate(zip(all_bands(W), volume_ref.threshold(before, L, "soft", 17.25, 1, 1))):
         assert ops_ref.same_bits(g, w), (case, num)
+
+
+# ------------------------------------------------------------------------------------------ every name of the wavelet table
+# The cases above are all orthogonal (rec is dec reversed): a volume that handed the wrong one of its dec / rec banks to a pass, or
+# indexed it mirrored, would pass them.  Every name of the table goes through a volume here -- bior* and rbio* are the first
+# biorthogonal ones --, one level, with the helpers and bounds of the tests above.  (13, 10, 14): planes of 140 samples, the wide
+# access in fp32; (6, 9, 11): planes of 99 samples, one column per lane, a depth below most of these filters' lengths.
+NAMES = list(oracle.filter_table()["order"])
+BIORTHOGONAL = [w for w in NAMES if w[:4] in ("bior", "rbio", "coif")]
+NAMES64 = ["bior3.9", "rbio6.8", "coif2"]
+WIDE_SHAPE, NARROW_SHAPE = (13, 10, 14), (6, 9, 11)
+
+
+def name_case(classes, dtype, shape, wname, width):
+    """One level of `wname` on `shape`: the forward against the composition, then the inverse alone from random coefficients.  A name
+    whose table length is odd is refused with PDWT_ERR_UNSUPPORTED (the depth kernels are built for even lengths)."""
+    case = (shape, wname, 1)
+    hlen = volume_ref.hlen_of(wname)
+    if hlen & 1:
+        with pytest.raises(NotImplementedError):
+            classes[dtype](np.zeros(shape, dtype=dtype), wname, 1)
+        return
+    r = ref_of(case)
+    assert r["levels"] == 1
+    W = classes[dtype](r["x"].astype(dtype), wname, 1)
+    assert (W.levels, W.hlen, W.nbands) == (1, hlen, 8)
+    assert W.depth_schedule(1)[0] == width, (case, W.depth_schedule(1))
+    W.forward()
+    for num, g in enumerate(all_bands(W)):
+        if dtype == np.float32:
+            close32(g, r["fwd64"][num], r["fwd32"][num], 1, (case, "band", num))
+        else:
+            ref = r["fwd64"][num]
+            assert g.dtype == np.float64 and g.shape == ref.shape
+            assert np.abs(g - ref).max() <= 1e-12 * max(1.0, float(np.abs(ref).max())), (case, num)
+    for num, c in enumerate(r["coef"]):
+        W.set_coeff(c.astype(dtype), num)
+    W.inverse()
+    if dtype == np.float32:
+        close32(W.image, r["inv64"], r["inv32"], 1, (case, "inverse"))
+    else:
+        assert np.abs(W.image - r["inv64"]).max() <= 1e-12 * max(1.0, float(np.abs(r["inv64"]).max())), case
+
+
+def test_the_table_has_72_names_and_the_biorthogonal_ones_are_among_them():
+    assert len(NAMES) == 72 and len(BIORTHOGONAL) == 33
+    assert sum(w.startswith("bior") for w in NAMES) == 14 and sum(w.startswith("rbio") for w in NAMES) == 14
+
+
+@pytest.mark.parametrize("wname", NAMES)
+def test_every_wavelet_name_through_a_volume(classes, wname):
+    hlen = volume_ref.hlen_of(wname)
+    name_case(classes, np.float32, WIDE_SHAPE, wname, 4 if hlen <= 16 else 2)
+
+
+@pytest.mark.parametrize("wname", BIORTHOGONAL)
+def test_biorthogonal_and_coiflet_names_below_their_length(classes, wname):
+    name_case(classes, np.float32, NARROW_SHAPE, wname, 1)
+
+
+@pytest.mark.parametrize("shape", [WIDE_SHAPE, NARROW_SHAPE], ids=["13x10x14", "6x9x11"])
+@pytest.mark.parametrize("wname", NAMES64)
+def test_fp64_biorthogonal_names(classes, wname, shape):
+    hlen = volume_ref.hlen_of(wname)
+    name_case(classes, np.float64, shape, wname, (2 if hlen <= 16 else 1) if shape == WIDE_SHAPE else 1)
