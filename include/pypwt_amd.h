@@ -336,7 +336,7 @@ const char* pdwt_comm_last_error(void);
  *   - pointers from pdwt_volume_image_ptr / pdwt_volume_coeff_ptr are borrowed and valid while the volume lives.
  * pdwt_volume_layout is a pure host function (no device needed): the clamped level count into *nlevels, (depth, rows, cols) of
  * num 0 .. capacity - 1 into dims[3 num + {0,1,2}]; returns the number of bands 1 + 7 L, or a negative status.
- * Out of scope: 3D SWT, non-separable volumes, custom filter banks, cycle spinning, clone and add_wavelet, shrink / group /
+ * Out of scope: 3D SWT through this constructor (pdwt_volume_create_swt below is the stationary transform), non-separable volumes, custom filter banks, cycle spinning, clone and add_wavelet, shrink / group /
  * proj_linf, the compiled Cython class, ShardedBatch / TiledWavelets for volumes, a fused kernel that does all three axes in
  * one read, a fused stats + threshold sweep. */
 typedef struct pdwt_volume* pdwt_volume_handle;
@@ -364,6 +364,33 @@ void* pdwt_volume_stream(pdwt_volume_handle h);
  * and inverse (one step = one low and one high slice forward, two output slices inverse).  Any pointer may be NULL.  Diagnostics,
  * like pdwt_schedule_string for a 2D plan. */
 int pdwt_volume_depth_schedule(pdwt_volume_handle h, int level, int* width, int* seg_fwd, int* seg_inv);
+
+/* ---- NEW: the STATIONARY (undecimated, a-trous) 3D transform of a volume: the translation-invariant transform of
+ * pywt.swtn / pywt.iswtn with axes taken in the order z, y, x, the formulas of the 2D SWT of this library on every axis (analysis
+ * centre hlen/2 - 1, synthesis centre hlen/2 with the factor 1/2 inside it, dilation 2^(l-1) at level l, periodic).
+ * pdwt_volume_create_swt takes pdwt_volume_create's arguments and returns the same kind of handle; every pdwt_volume_* call
+ * above serves it with these differences:
+ *   - every band has the image's shape (Nz, Nr, Nc); numbering and keys are unchanged: 0 = A_L ('aaa' of the last level), then
+ *     1 + 7 (l - 1) + k over aad .. ddd, level 1 the finest.  pywt.swtn's list is, coarsest level first, a dict per level with
+ *     those seven keys and 'aaa'; the 'aaa' of a level below L is an intermediate this handle does not expose;
+ *   - sizes: every axis >= 2 (any parity: the transform is periodic in the true length), Nz <= 32767 (PDWT_ERR_ARG), even
+ *     filters only (PDWT_ERR_UNSUPPORTED); levels are clamped as for pdwt_volume_create;
+ *   - footprint: ONE device block of (3 + 8 L) volumes -- the image, a stack of 2 Nz slices shared by all levels and four
+ *     arrays of 2 Nz slices per level -- plus 256-B alignment of each buffer and a few KiB; a failed allocation returns
+ *     PDWT_ERR_NOMEM and leaves nothing behind.  pdwt_volume_layout_swt is a pure host function (no device needed): the clamped
+ *     level count into *nlevels and the size of that block into *device_bytes for values of sizeof_real bytes (4, 8, or 0 = this
+ *     library's pdwt_real); returns the number of bands 1 + 7 L, or a negative status;
+ *   - state machine, soft / hard threshold (per-level thresholds as above) and pdwt_volume_norms (A_L and the 7 L details) are
+ *     the decimated volume's; sub-bands of 2^31 elements and more: the thresholds and norms return PDWT_ERR_UNSUPPORTED;
+ *   - pdwt_volume_depth_schedule: columns per thread of the depth ANALYSIS (the synthesis holds twice the window and may take
+ *     fewer), and the steps per segment of an orbit walk g -> (g + 2^(l-1)) mod Nz, one output slice per step and direction;
+ *   - the adaptive and K-term operators below (band_stats, norms_async, estimate_sigma, threshold_bands, denoise,
+ *     adaptive_slots, select_magnitude, keep_largest, sparsify_slots) return PDWT_ERR_UNSUPPORTED with a message naming the call.
+ * pdwt_volume_is_swt: 1 for such a handle, 0 for a decimated volume. */
+int pdwt_volume_create_swt(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host,
+                           int device_id, void* hip_stream, pdwt_volume_handle* out);
+int pdwt_volume_is_swt(pdwt_volume_handle h);
+int pdwt_volume_layout_swt(int Nz, int Nr, int Nc, const char* wname, int levels, int* nlevels, long long* device_bytes, int sizeof_real);
 
 /* The adaptive and the K-term operators (pdwt_band_stats_async ... pdwt_keep_largest_async above) on a volume.  A volume is ONE
  * image: its bands are the 1 + 7 L sub-bands in `num` order, the slices and levels of a sub-band are pooled on the device, and the

@@ -126,6 +126,11 @@ def signatures(real=C.c_float):
         "pdwt_comm_last_error": (C.c_char_p, []),
         "pdwt_volume_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.POINTER(handle_t)]),
+        "pdwt_volume_create_swt": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.POINTER(handle_t)]),
+        "pdwt_volume_is_swt": (C.c_int, [handle_t]),
+        "pdwt_volume_layout_swt": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong),
+                                             C.c_int]),
         "pdwt_volume_destroy": (C.c_int, [handle_t]),
         "pdwt_volume_forward": (C.c_int, [handle_t]),
         "pdwt_volume_inverse": (C.c_int, [handle_t]),

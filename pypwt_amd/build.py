@@ -47,6 +47,7 @@ SOURCES = [
     "launch_dwt2_ring.hip",
     "launch_dwt2_long.hip",
     "launch_dwt3.hip",
+    "launch_swt3.hip",
     "launch_dwt1.hip",
     "launch_dwt1_fused.hip",
     "launch_dwt1_reg.hip",

@@ -133,6 +133,17 @@ hipError_t launch_dwt3_depth_fwd(const real_t* in, real_t* out, int Nz, long lon
                                  hipStream_t s);
 hipError_t launch_dwt3_depth_inv(const real_t* in, real_t* out, int Nz, long long P, int hlen, const FilterBank& fb, int seg,
                                  hipStream_t s);
+// one UNDECIMATED level along the slowest axis of a volume at dilation f (swt3_axis_kernels.hpp): forward in [Nz][P] -> out [2 Nz][P]
+// (low slices, then high slices); inverse the other way round.  Even hlen of the built-in table; seg = steps per segment of an orbit
+// walk (swt3_depth_steps outputs per orbit), from swt3_depth_seg for the width swt3_depth_width answers
+int swt3_depth_width(const void* in, const void* out, long long P, int hlen, bool inverse);
+int swt3_depth_steps(int Nz, int f);
+int swt3_depth_seg(int Nz, int f, long long P, int hlen, int width, int slots);
+int swt3_depth_slots(int hlen, int width, bool inverse);
+hipError_t launch_swt3_depth_fwd(const real_t* in, real_t* out, int Nz, long long P, int f, int hlen, const FilterBank& fb, int seg,
+                                 hipStream_t s);
+hipError_t launch_swt3_depth_inv(const real_t* in, real_t* out, int Nz, long long P, int f, int hlen, const FilterBank& fb, int seg,
+                                 hipStream_t s);
 hipError_t launch_dwt1_fwd(const Fwd1DArgs& a, hipStream_t s);
 hipError_t launch_dwt1_inv(const Inv1DArgs& a, hipStream_t s);
 // K consecutive 1D levels in one launch (2^K must divide N0, even hlen); hipErrorNotSupported otherwise
@@ -150,7 +161,9 @@ hipError_t launch_dwt1_fwd_fused(const real_t* in, real_t* const* det, real_t* a
                                  const FilterBank& fb, hipStream_t s);
 hipError_t launch_dwt1_inv_fused(const real_t* app, const real_t* const* det, real_t* out, int rows, int N0, int K,
                                  int hlen, const FilterBank& fb, hipStream_t s);
-// fused a-trous level; the host guarantees a.f divides a.Nr
+// fused a-trous level at any dilation a.f >= 1 and any (Nr, Nc): where a.f does not divide a.Nr the tiles wrap ROWS, not phase
+// indices (launch_swt.hip: run_fwd / run_inv), and an index further out than one period falls back to a true modulo
+// (wrap_periodic).  The stationary volume relies on both: (5, 7, 9) at level 2 is f = 2 on 7 rows, and planes below the filter length.
 hipError_t launch_swt2_fwd(const Swt2DArgs& a, int batch, hipStream_t s);
 hipError_t launch_swt2_inv(const Swt2DArgs& a, int batch, hipStream_t s);
 bool swt2_fwd_stream_takes(const Swt2DArgs& a, int batch);  // the one-launch forward level of swt_fwdstream_kernels.hpp would take this level

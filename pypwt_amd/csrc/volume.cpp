@@ -2,7 +2,8 @@
 // (launch_dwt3.hip) around one-level batched 2D plans (volume.hpp has the layout).  The 2D side goes through the plans' own
 // entry points -- pdwt_create_batched, pdwt_forward / pdwt_inverse, pdwt_threshold_bands, pdwt_band_stats_async --, so nothing
 // a 1D or 2D plan does is restated here.  The adaptive and K-term operators pool the slices and levels of a sub-band on the device
-// (volume_ops_kernels.hpp, launch_volume_ops.hip): a volume is ONE image.
+// (volume_ops_kernels.hpp, launch_volume_ops.hip): a volume is ONE image.  The STATIONARY volume (pdwt_volume_create_swt) has no level
+// plans: a-trous depth passes (launch_swt3.hip) around the batched 2D SWT launchers of launch.hpp, called directly, on one device block.
 #include "volume.hpp"
 
 #include <math.h>
@@ -317,8 +318,276 @@ int select_magnitude_impl(pdwt_volume* v, long long k, int do_app, real_t* d_thr
     return PDWT_OK;
 }
 
+
+// ---------------------------------------------------------------- the stationary volume (volume.hpp: do_swt)
+int check_shape_swt(const char* what, int Nz, int Nr, int Nc, const char* wname, const WaveletEntry** w) {
+    if (Nz < 2 || Nr < 2 || Nc < 2) return VFAIL(PDWT_ERR_ARG, "%s: every axis needs at least 2 samples, got (%d, %d, %d)", what, Nz, Nr, Nc);
+    // the batched 2D level runs 2 Nz planes in gridDim.z
+    if (Nz > 32767) return VFAIL(PDWT_ERR_ARG, "%s: depth %d is beyond the limit of 32767 slices", what, Nz);
+    if (!wname) return VFAIL(PDWT_ERR_ARG, "%s: wname is null", what);
+    *w = find_wavelet(wname);
+    if (!*w) return VFAIL(PDWT_ERR_WAVELET, "unknown wavelet name %s", wname);
+    if ((*w)->hlen & 1) return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: filters of odd length are not built for volumes", what);
+    return PDWT_OK;
+}
+
+// the one device block of a stationary volume, in bytes from its start (volume.hpp has the picture); no HIP call
+struct SwtLayout {
+    size_t image = 0, stack = 0, bands = 0, band = 0, stats = 0, partial = 0, table = 0, total = 0;
+    long long chunk = 0;
+    int pieces = 0;
+};
+
+SwtLayout swt_layout(int Nz, int Nr, int Nc, int L, size_t real_bytes) {
+    SwtLayout y;
+    const long long n = (long long)Nz * Nr * Nc;  // one volume = one depth half of a band array
+    const size_t vol = align256((size_t)n * real_bytes);
+    y.band = align256((size_t)2 * n * real_bytes);
+    y.image = 0;
+    y.stack = vol;
+    y.bands = y.stack + y.band;
+    // sweep geometry of ONE level (threshold and sums alike): about 1024 pieces of at least 4096 values, each inside one half
+    y.chunk = ((8 * n + 1023) / 1024 + 1023) / 1024 * 1024;
+    if (y.chunk < 4096) y.chunk = 4096;
+    y.pieces = (int)(8 * ((n + y.chunk - 1) / y.chunk));
+    y.stats = y.bands + (size_t)4 * L * y.band;
+    y.partial = y.stats + align256((size_t)L * 16 * sizeof(double));
+    y.table = y.partial + align256((size_t)L * 2 * y.pieces * sizeof(double));
+    y.total = y.table + align256((size_t)L * 8 * real_bytes) + 256;  // slack: the one-launch 2D kernels may read 12 B past a plane
+    return y;
+}
+
+real_t* swt_sub_ptr(const pdwt_volume* v, const SubBand& s) {
+    return v->swt_band[4 * (s.level - 1) + s.band] + (long long)s.half * elems(s);
+}
+
+real_t* swt_approx_ptr(const pdwt_volume* v, int l) { return l == 0 ? v->image : v->swt_band[4 * (l - 1)]; }
+
+// host <-> device copies on the volume's stream, as pdwt_copy does for a plan (kind 0 d2d, 1 h2d, 2 d2h)
+int swt_copy(pdwt_volume* v, void* dst, const void* src, long long count, int kind) {
+    if (count == 0) return PDWT_OK;
+    const hipMemcpyKind k = kind == 0 ? hipMemcpyDeviceToDevice : (kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
+    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)count * sizeof(real_t), k, v->stream));
+    if (kind != 0) HIP_TRY(hipStreamSynchronize(v->stream));
+    return PDWT_OK;
+}
+
+Swt2DArgs swt_level_args(const pdwt_volume* v, int l, bool inverse) {
+    Swt2DArgs a;
+    real_t* const* b = &v->swt_band[4 * (l - 1)];
+    a.in = inverse ? nullptr : v->swt_stack;
+    a.A = b[0], a.H = b[1], a.V = b[2], a.D = b[3];
+    a.out = inverse ? v->swt_stack : nullptr;
+    a.Nr = v->Nr, a.Nc = v->Nc, a.f = 1 << (l - 1);
+    a.bstride = (long long)v->Nr * v->Nc;
+    a.hlen = v->hlen;
+    a.soft_beta = 0;
+    a.fb = inverse ? v->rec : v->dec;
+    return a;
+}
+
+int swt_forward(pdwt_volume* v) {
+    const long long P = (long long)v->Nr * v->Nc;
+    const int B = 2 * v->Nz;
+    for (int l = 1; l <= v->nlevels; l++) {
+        hipError_t e = launch_swt3_depth_fwd(swt_approx_ptr(v, l - 1), v->swt_stack, v->Nz, P, 1 << (l - 1), v->hlen, v->dec, v->seg_fwd[l - 1], v->stream);
+        if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "depth analysis of level %d failed: %s", l, hipGetErrorString(e));
+        const Swt2DArgs a = swt_level_args(v, l, false);
+        // the one-launch level first (plan.cpp: fwd_level_2d); hipErrorNotSupported is a decline
+        e = swt2_fwd_stream_takes(a, B) ? try_launch_swt2_fwd_stream(a, B, v->stream) : hipErrorNotSupported;
+        if (e == hipErrorNotSupported) e = launch_swt2_fwd(a, B, v->stream);
+        if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "2D analysis of level %d failed: %s", l, hipGetErrorString(e));
+    }
+    return PDWT_OK;
+}
+
+int swt_inverse(pdwt_volume* v) {
+    const long long P = (long long)v->Nr * v->Nc;
+    const int B = 2 * v->Nz;
+    for (int l = v->nlevels; l >= 1; l--) {
+        const Swt2DArgs a = swt_level_args(v, l, true);
+        hipError_t e = swt2_inv_stream_takes(a, B) ? try_launch_swt2_inv_stream(a, B, v->stream) : hipErrorNotSupported;
+        if (e == hipErrorNotSupported) e = launch_swt2_inv(a, B, v->stream);
+        if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "2D synthesis of level %d failed: %s", l, hipGetErrorString(e));
+        e = launch_swt3_depth_inv(v->swt_stack, swt_approx_ptr(v, l - 1), v->Nz, P, 1 << (l - 1), v->hlen, v->rec, v->seg_inv[l - 1], v->stream);
+        if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "depth synthesis of level %d failed: %s", l, hipGetErrorString(e));
+    }
+    return PDWT_OK;
+}
+
+// the sweeps see a level as 4 bands x 2 "images" of Nz P values; bands of 2^31 values and more are beyond their index math
+int swt_ops_check(const pdwt_volume* v, const char* what) {
+    if ((long long)v->Nz * v->Nr * v->Nc >= (1LL << 31))
+        return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: sub-bands of %lld elements are beyond the operators' limit of 2^31 - 1", what, (long long)v->Nz * v->Nr * v->Nc);
+    return PDWT_OK;
+}
+
+int swt_threshold(pdwt_volume* v, int op, real_t beta, int do_app, int normalize, const char* what) {
+    if (v->state == PDWT_INVERSE)
+        return VFAIL(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what);
+    PDWT_TRY(swt_ops_check(v, what));
+    DeviceGuard guard(v->device);
+    const int L = v->nlevels;
+    const real_t leave = std::numeric_limits<real_t>::quiet_NaN();  // launch_threshold_bands: a NaN entry leaves that pair alone
+    HIP_TRY(hipEventSynchronize(v->swt_staged));  // the previous table has left the pinned buffer
+    real_t* table = v->swt_h_table;
+    real_t b = beta;
+    for (int l = 1; l <= L; l++) {
+        if (normalize > 0) b = (real_t)(b / 1.4142135623730951);  // plan.cpp: threshold_sweep (common.cu:244)
+        for (int k = 0; k < 8; k++) table[8 * (l - 1) + k] = b;
+        table[8 * (l - 1)] = (l == L && do_app) ? app_beta(beta, L, normalize) : leave;  // aaa: A_L, or an intermediate
+    }
+    HIP_TRY(hipMemcpyAsync(v->swt_table, table, (size_t)8 * L * sizeof(real_t), hipMemcpyHostToDevice, v->stream));
+    HIP_TRY(hipEventRecord(v->swt_staged, v->stream));
+    for (int l = 1; l <= L; l++)
+        HIP_TRY(launch_threshold_bands(op, reinterpret_cast<real_t*>(v->swt_block), v->swt_bt[l - 1], v->swt_table + 8 * (l - 1), v->stream));
+    return PDWT_OK;
+}
+
+int swt_norms(pdwt_volume* v, double out[2]) {
+    if (v->state == PDWT_INVERSE) return VFAIL(PDWT_ERR_STATE, "norms: the coefficients were modified by inverse()");
+    PDWT_TRY(swt_ops_check(v, "norms"));
+    DeviceGuard guard(v->device);
+    const int L = v->nlevels;
+    for (int l = 1; l <= L; l++)
+        HIP_TRY(launch_band_stats(reinterpret_cast<const real_t*>(v->swt_block), v->swt_bt[l - 1], v->swt_partial + (size_t)2 * v->swt_pieces * (l - 1),
+                                  v->swt_stats + 16 * (l - 1), v->stream));
+    std::vector<double> sums((size_t)16 * L);
+    HIP_TRY(hipMemcpyAsync(sums.data(), v->swt_stats, sums.size() * sizeof(double), hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    // [level][band][half][2]: all details, and aaa at the last level only, in a fixed order, in double
+    double n1 = 0, n2 = 0;
+    for (int l = 1; l <= L; l++)
+        for (int k = 0; k < 8; k++) {
+            if (k == 0 && l != L) continue;
+            n1 += sums[(size_t)16 * (l - 1) + 2 * k];
+            n2 += sums[(size_t)16 * (l - 1) + 2 * k + 1];
+        }
+    out[0] = n1, out[1] = n2;
+    return PDWT_OK;
+}
+
+void destroy(pdwt_volume* v);
+
+int swt_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host, int device_id, void* hip_stream,
+               pdwt_volume_handle* out) {
+    const char* what = "pdwt_volume_create_swt";
+    if (!out) return VFAIL(PDWT_ERR_ARG, "%s: out is null", what);
+    *out = nullptr;
+    const WaveletEntry* w = nullptr;
+    PDWT_TRY(check_shape_swt(what, Nz, Nr, Nc, wname, &w));
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return VFAIL(PDWT_ERR_HIP, "no HIP device available (this library has no CPU path)");
+    if (device_id < 0) HIP_TRY(hipGetDevice(&device_id));
+    if (device_id >= ndev) return VFAIL(PDWT_ERR_ARG, "device %d out of range (%d devices)", device_id, ndev);
+
+    pdwt_volume* v = new pdwt_volume();
+    v->do_swt = 1;
+    v->device = device_id;
+    v->Nz = Nz, v->Nr = Nr, v->Nc = Nc;
+    v->hlen = w->hlen;
+    v->nlevels = clamp_levels(Nz, Nr, Nc, wname, w->hlen, levels, true);
+    snprintf(v->wname, sizeof(v->wname), "%s", wname);
+    for (int i = 0; i < kMaxTaps; i++) {
+        const bool in = i < w->hlen;
+        v->dec.lo[i] = in ? (real_t)w->dec_lo[i] : 0, v->dec.hi[i] = in ? (real_t)w->dec_hi[i] : 0;
+        v->rec.lo[i] = in ? (real_t)w->rec_lo[i] : 0, v->rec.hi[i] = in ? (real_t)w->rec_hi[i] : 0;
+    }
+    DeviceGuard guard(device_id);
+    auto bail = [&](int code) {
+        destroy(v);
+        return code;
+    };
+    const int L = v->nlevels;
+    v->nz.assign(L + 1, Nz), v->nr.assign(L + 1, Nr), v->nc.assign(L + 1, Nc);
+    if (hip_stream) {
+        v->stream = (hipStream_t)hip_stream;
+    } else {
+        const hipError_t e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            v->stream = nullptr;
+            VFAIL(PDWT_ERR_HIP, "%s: hipStreamCreate: %s", what, hipGetErrorString(e));
+            return bail(PDWT_ERR_HIP);
+        }
+        v->own_stream = true;
+    }
+    const SwtLayout y = swt_layout(Nz, Nr, Nc, L, sizeof(real_t));
+    hipError_t e = hipMalloc(&v->swt_block, y.total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        v->swt_block = nullptr;
+        VFAIL(PDWT_ERR_NOMEM, "%s: hipMalloc of %zu bytes failed: %s", what, y.total, hipGetErrorString(e));
+        return bail(PDWT_ERR_NOMEM);
+    }
+    char* base = static_cast<char*>(v->swt_block);
+    v->image = reinterpret_cast<real_t*>(base + y.image);
+    v->swt_stack = reinterpret_cast<real_t*>(base + y.stack);
+    for (int k = 0; k < 4 * L; k++) v->swt_band.push_back(reinterpret_cast<real_t*>(base + y.bands + (size_t)k * y.band));
+    v->swt_stats = reinterpret_cast<double*>(base + y.stats);
+    v->swt_partial = reinterpret_cast<double*>(base + y.partial);
+    v->swt_table = reinterpret_cast<real_t*>(base + y.table);
+    v->swt_pieces = y.pieces;
+    const long long n = (long long)Nz * Nr * Nc;
+    for (int l = 1; l <= L; l++) {
+        BandTable t{};
+        t.nbands = 4;
+        t.batch = 2;
+        t.chunk = y.chunk;
+        for (int b = 0; b < 4; b++) {
+            t.off[b] = (long long)((y.bands + (size_t)(4 * (l - 1) + b) * y.band) / sizeof(real_t));
+            t.n[b] = n;
+            t.blk[b] = b * (y.pieces / 4);
+        }
+        t.blk[4] = y.pieces;
+        v->swt_bt.push_back(t);
+    }
+    const size_t bytes = (size_t)n * sizeof(real_t);
+    // everything behind the image starts as zeros: coefficients that were never computed read as 0, like a plan's arena
+    e = hipMemsetAsync(base + y.stack, 0, y.total - y.stack, v->stream);
+    if (e == hipSuccess)
+        e = img ? hipMemcpyAsync(v->image, img, bytes, mem_is_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, v->stream)
+                : hipMemsetAsync(v->image, 0, bytes, v->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(v->stream);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&v->swt_h_table, (size_t)8 * L * sizeof(real_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->swt_staged, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        VFAIL(PDWT_ERR_HIP, "%s: image upload failed: %s", what, hipGetErrorString(e));
+        return bail(PDWT_ERR_HIP);
+    }
+    // orbit segments: fixed with the layout (every buffer is 256-B aligned, so the widths depend on the plane size only)
+    const long long P = (long long)Nr * Nc;
+    for (int l = 1; l <= L; l++) {
+        const int f = 1 << (l - 1);
+        const int wf = swt3_depth_width(swt_approx_ptr(v, l - 1), v->swt_stack, P, v->hlen, false);
+        const int wi = swt3_depth_width(v->swt_stack, swt_approx_ptr(v, l - 1), P, v->hlen, true);
+        v->width.push_back(wf);
+        v->width_inv.push_back(wi);
+        v->seg_fwd.push_back(swt3_depth_seg(Nz, f, P, v->hlen, wf, swt3_depth_slots(v->hlen, wf, false)));
+        v->seg_inv.push_back(swt3_depth_seg(Nz, f, P, v->hlen, wi, swt3_depth_slots(v->hlen, wi, true)));
+    }
+    v->seg_fwd_chosen = v->seg_fwd, v->seg_inv_chosen = v->seg_inv;
+    *out = v;
+    return PDWT_OK;
+}
+
+int swt_unsupported(const char* what) {
+    return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: the adaptive and K-term operators are not built for stationary volumes (do_swt)", what);
+}
+
 void destroy(pdwt_volume* v) {
     DeviceGuard guard(v->device);
+    if (v->do_swt) {
+        if (v->stream) (void)hipStreamSynchronize(v->stream);
+        if (v->swt_block) (void)hipFree(v->swt_block);
+        if (v->swt_h_table) (void)hipHostFree(v->swt_h_table);
+        if (v->swt_staged) (void)hipEventDestroy(v->swt_staged);
+        if (v->own_stream && v->stream) (void)hipStreamDestroy(v->stream);
+        delete v;
+        return;
+    }
     if (!v->plans.empty()) (void)hipStreamSynchronize(v->stream);
     if (VolumeWs* w = v->ops) {
         if (w->block) (void)hipFree(w->block);
@@ -424,6 +693,24 @@ int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char*
     return PDWT_OK;
 }
 
+int pdwt_volume_create_swt(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host,
+                           int device_id, void* hip_stream, pdwt_volume_handle* out) {
+    return swt_create(img, Nz, Nr, Nc, wname, levels, mem_is_on_host, device_id, hip_stream, out);
+}
+
+int pdwt_volume_is_swt(pdwt_volume_handle v) { return v ? v->do_swt : VFAIL(PDWT_ERR_ARG, "null volume handle"); }
+
+int pdwt_volume_layout_swt(int Nz, int Nr, int Nc, const char* wname, int levels, int* nlevels, long long* device_bytes, int sizeof_real) {
+    const WaveletEntry* w = nullptr;
+    PDWT_TRY(check_shape_swt("pdwt_volume_layout_swt", Nz, Nr, Nc, wname, &w));
+    if (sizeof_real != 0 && sizeof_real != 4 && sizeof_real != 8)
+        return VFAIL(PDWT_ERR_ARG, "pdwt_volume_layout_swt: sizeof_real must be 4, 8 or 0 (this library's), got %d", sizeof_real);
+    const int L = clamp_levels(Nz, Nr, Nc, wname, w->hlen, levels, false);
+    if (nlevels) *nlevels = L;
+    if (device_bytes) *device_bytes = (long long)swt_layout(Nz, Nr, Nc, L, sizeof_real ? (size_t)sizeof_real : sizeof(real_t)).total;
+    return 1 + 7 * L;
+}
+
 int pdwt_volume_destroy(pdwt_volume_handle v) {
     if (!v) return PDWT_OK;
     destroy(v);
@@ -433,6 +720,11 @@ int pdwt_volume_destroy(pdwt_volume_handle v) {
 int pdwt_volume_forward(pdwt_volume_handle v) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
     DeviceGuard guard(v->device);
+    if (v->do_swt) {
+        const int rc = swt_forward(v);
+        v->state = rc == PDWT_OK ? PDWT_FORWARD : PDWT_FORWARD_ERROR;
+        return rc;
+    }
     for (int l = 1; l <= v->nlevels; l++) {
         pdwt_handle p = v->plans[l - 1];
         real_t* stack = stack_ptr(v, l);
@@ -457,6 +749,11 @@ int pdwt_volume_inverse(pdwt_volume_handle v) {
     if (v->state == PDWT_FORWARD_ERROR || v->state == PDWT_THRESHOLD_ERROR || v->state == PDWT_CREATION_ERROR)
         return VFAIL(PDWT_ERR_STATE, "inverse transform not computed, as there was an error in a previous stage");
     DeviceGuard guard(v->device);
+    if (v->do_swt) {
+        const int rc = swt_inverse(v);
+        v->state = rc == PDWT_OK ? PDWT_INVERSE : PDWT_INVERSE_ERROR;
+        return rc;
+    }
     for (int l = v->nlevels; l >= 1; l--) {
         pdwt_handle p = v->plans[l - 1];
         // band A's depth-low half was written in place: by the level below, by the forward or by set_coeff
@@ -491,7 +788,8 @@ long long pdwt_volume_get_image(pdwt_volume_handle v, pdwt_real* dst) {
     if (!v || !dst) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_get_image: null argument");
     DeviceGuard guard(v->device);
     const long long n = (long long)v->Nz * v->Nr * v->Nc;
-    PDWT_TRY(pdwt_copy(v->plans[0], dst, v->image, n, 2));
+    if (v->do_swt) PDWT_TRY(swt_copy(v, dst, v->image, n, 2));
+    else PDWT_TRY(pdwt_copy(v->plans[0], dst, v->image, n, 2));
     return n;
 }
 
@@ -500,7 +798,8 @@ int pdwt_volume_set_image(pdwt_volume_handle v, const pdwt_real* src, int mem_is
     DeviceGuard guard(v->device);
     const long long n = (long long)v->Nz * v->Nr * v->Nc;
     if (!(mem_is_on_device && src == v->image)) {
-        PDWT_TRY(pdwt_copy(v->plans[0], v->image, src, n, mem_is_on_device ? 0 : 1));
+        if (v->do_swt) PDWT_TRY(swt_copy(v, v->image, src, n, mem_is_on_device ? 0 : 1));
+        else PDWT_TRY(pdwt_copy(v->plans[0], v->image, src, n, mem_is_on_device ? 0 : 1));
         if (mem_is_on_device) HIP_TRY(hipStreamSynchronize(v->stream));  // like pdwt_set_image: the source may be reused at once
     }
     v->state = PDWT_INIT;
@@ -526,7 +825,8 @@ long long pdwt_volume_get_coeff(pdwt_volume_handle v, pdwt_real* dst, int num) {
         return 0;
     }
     DeviceGuard guard(v->device);
-    PDWT_TRY(pdwt_copy(v->plans[s.level - 1], dst, sub_ptr(v, s), elems(s), 2));
+    if (v->do_swt) PDWT_TRY(swt_copy(v, dst, swt_sub_ptr(v, s), elems(s), 2));
+    else PDWT_TRY(pdwt_copy(v->plans[s.level - 1], dst, sub_ptr(v, s), elems(s), 2));
     return elems(s);
 }
 
@@ -535,9 +835,10 @@ int pdwt_volume_set_coeff(pdwt_volume_handle v, const pdwt_real* src, int num, i
     SubBand s;
     if (!locate(v, num, &s)) return VFAIL(PDWT_ERR_ARG, "coefficient index %d out of range", num);
     DeviceGuard guard(v->device);
-    real_t* dst = sub_ptr(v, s);
+    real_t* dst = v->do_swt ? swt_sub_ptr(v, s) : sub_ptr(v, s);
     if (!(mem_is_on_device && src == dst)) {
-        PDWT_TRY(pdwt_copy(v->plans[s.level - 1], dst, src, elems(s), mem_is_on_device ? 0 : 1));
+        if (v->do_swt) PDWT_TRY(swt_copy(v, dst, src, elems(s), mem_is_on_device ? 0 : 1));
+        else PDWT_TRY(pdwt_copy(v->plans[s.level - 1], dst, src, elems(s), mem_is_on_device ? 0 : 1));
         if (mem_is_on_device) HIP_TRY(hipStreamSynchronize(v->stream));
     }
     // as pdwt_set_coeff: once the approximation has been supplied again the coefficients are current
@@ -551,21 +852,24 @@ intptr_t pdwt_volume_coeff_ptr(pdwt_volume_handle v, int num) {
     SubBand s;
     if (!v || !locate(v, num, &s)) return 0;
     DeviceGuard guard(v->device);
-    return (intptr_t)sub_ptr(v, s);
+    return (intptr_t)(v->do_swt ? swt_sub_ptr(v, s) : sub_ptr(v, s));
 }
 
 int pdwt_volume_soft_threshold(pdwt_volume_handle v, pdwt_real beta, int do_thresh_appcoeffs, int normalize) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_threshold(v, EW_SOFT, beta, do_thresh_appcoeffs, normalize, "soft_threshold");
     return threshold_impl(v, EW_SOFT, beta, do_thresh_appcoeffs, normalize, "soft_threshold");
 }
 
 int pdwt_volume_hard_threshold(pdwt_volume_handle v, pdwt_real beta, int do_thresh_appcoeffs, int normalize) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_threshold(v, EW_HARD, beta, do_thresh_appcoeffs, normalize, "hard_threshold");
     return threshold_impl(v, EW_HARD, beta, do_thresh_appcoeffs, normalize, "hard_threshold");
 }
 
 int pdwt_volume_norms(pdwt_volume_handle v, double out[2]) {
     if (!v || !out) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_norms: null argument");
+    if (v->do_swt) return swt_norms(v, out);
     if (v->state == PDWT_INVERSE)
         return VFAIL(PDWT_ERR_STATE, "norms: the coefficients were modified by inverse()");
     DeviceGuard guard(v->device);
@@ -598,6 +902,7 @@ int pdwt_volume_norms(pdwt_volume_handle v, double out[2]) {
 // ---------------------------------------------------------------- NEW: the adaptive and K-term operators on ONE volume
 int pdwt_volume_band_stats_async(pdwt_volume_handle v, double* d_out) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_band_stats_async");
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "band_stats", false));
     return band_stats_impl(v, d_out);
@@ -605,6 +910,7 @@ int pdwt_volume_band_stats_async(pdwt_volume_handle v, double* d_out) {
 
 int pdwt_volume_norms_async(pdwt_volume_handle v, double* d_out2) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_norms_async");
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "norms", false));
     PDWT_TRY(band_stats_impl(v, nullptr));
@@ -614,6 +920,7 @@ int pdwt_volume_norms_async(pdwt_volume_handle v, double* d_out2) {
 
 int pdwt_volume_estimate_sigma_async(pdwt_volume_handle v, int skip_zeros, double* d_out) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_estimate_sigma_async");
     DeviceGuard guard(v->device);
     PDWT_TRY(noise_check(v, "estimate_sigma"));
     PDWT_TRY(enter_ops(v, "estimate_sigma", false));
@@ -622,6 +929,7 @@ int pdwt_volume_estimate_sigma_async(pdwt_volume_handle v, int skip_zeros, doubl
 
 int pdwt_volume_threshold_bands(pdwt_volume_handle v, int op, const pdwt_real* table, int table_on_device) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_threshold_bands");
     if (!table) return VFAIL(PDWT_ERR_ARG, "threshold_bands: null table");
     if (op != EW_SOFT && op != EW_HARD) return VFAIL(PDWT_ERR_ARG, "threshold_bands: op must be 0 (soft) or 1 (hard)");
     DeviceGuard guard(v->device);
@@ -647,6 +955,7 @@ int pdwt_volume_threshold_bands(pdwt_volume_handle v, int op, const pdwt_real* t
 
 int pdwt_volume_denoise_async(pdwt_volume_handle v, int method, int op, const double* sigma, int skip_zeros) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_denoise_async");
     if (method != PDWT_DENOISE_BAYES && method != PDWT_DENOISE_VISU) return VFAIL(PDWT_ERR_ARG, "denoise: unknown method %d", method);
     if (op != EW_SOFT && op != EW_HARD) return VFAIL(PDWT_ERR_ARG, "denoise: op must be 0 (soft) or 1 (hard)");
     if (!sigma) PDWT_TRY(noise_check(v, "denoise"));
@@ -664,6 +973,7 @@ int pdwt_volume_denoise_async(pdwt_volume_handle v, int method, int op, const do
 
 int pdwt_volume_adaptive_slots(pdwt_volume_handle v, double** d_stats, double** d_sigma, pdwt_real** d_table) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_adaptive_slots");
     DeviceGuard guard(v->device);
     PDWT_TRY(ensure_ops(v));
     if (d_stats) *d_stats = v->ops->stats;
@@ -675,6 +985,7 @@ int pdwt_volume_adaptive_slots(pdwt_volume_handle v, double** d_stats, double** 
 int pdwt_volume_select_magnitude_async(pdwt_volume_handle v, long long k, int do_thresh_appcoeffs, pdwt_real* d_threshold,
                                        unsigned long long* d_kept) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_select_magnitude_async");
     PDWT_TRY(sparsify_check(v, "select_magnitude", k, do_thresh_appcoeffs));
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "select_magnitude", false));
@@ -683,6 +994,7 @@ int pdwt_volume_select_magnitude_async(pdwt_volume_handle v, long long k, int do
 
 int pdwt_volume_keep_largest_async(pdwt_volume_handle v, long long k, int do_thresh_appcoeffs) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_keep_largest_async");
     PDWT_TRY(sparsify_check(v, "keep_largest", k, do_thresh_appcoeffs));
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "keep_largest", true));
@@ -693,6 +1005,7 @@ int pdwt_volume_keep_largest_async(pdwt_volume_handle v, long long k, int do_thr
 
 int pdwt_volume_sparsify_slots(pdwt_volume_handle v, pdwt_real** d_threshold, unsigned long long** d_kept) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt) return swt_unsupported("pdwt_volume_sparsify_slots");
     DeviceGuard guard(v->device);
     PDWT_TRY(ensure_ops(v));
     if (d_threshold) *d_threshold = v->ops->sp_threshold;
@@ -734,7 +1047,7 @@ int pdwt_volume_set_filters(pdwt_volume_handle v, int hlen, const pdwt_real* dec
     if (hlen != v->hlen)
         return VFAIL(PDWT_ERR_ARG, "pdwt_volume_set_filters: %d taps, the volume was created with %d (the schedule is not rebuilt)", hlen, v->hlen);
     DeviceGuard guard(v->device);
-    // the level plans first: a plan that refuses leaves the volume's own bank as it was
+    // the level plans first: a plan that refuses leaves the volume's own bank as it was (a stationary volume has none)
     for (pdwt_handle p : v->plans) {
         PDWT_TRY(pdwt_set_filters_forward(p, nullptr, (unsigned)hlen, dec_lo, dec_hi, nullptr, nullptr));
         PDWT_TRY(pdwt_set_filters_inverse(p, rec_lo, rec_hi, nullptr, nullptr));
@@ -750,7 +1063,9 @@ int pdwt_volume_set_filters(pdwt_volume_handle v, int hlen, const pdwt_real* dec
 int pdwt_volume_set_depth_segments(pdwt_volume_handle v, int level, int seg_fwd, int seg_inv) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
     if (level < 1 || level > v->nlevels) return VFAIL(PDWT_ERR_ARG, "level %d out of range (1 .. %d)", level, v->nlevels);
-    const int steps_fwd = dwt3_depth_steps(v->nz[level - 1], v->hlen, false), steps_inv = dwt3_depth_steps(v->nz[level - 1], v->hlen, true);
+    // (a stationary volume: the steps of one orbit walk at the level's dilation, the same in both directions)
+    const int steps_fwd = v->do_swt ? swt3_depth_steps(v->Nz, 1 << (level - 1)) : dwt3_depth_steps(v->nz[level - 1], v->hlen, false),
+              steps_inv = v->do_swt ? steps_fwd : dwt3_depth_steps(v->nz[level - 1], v->hlen, true);
     if (seg_fwd < 0 || seg_fwd > steps_fwd || seg_inv < 0 || seg_inv > steps_inv)
         return VFAIL(PDWT_ERR_ARG, "pdwt_volume_set_depth_segments: (%d, %d) steps per segment, level %d walks (%d, %d) steps", seg_fwd, seg_inv,
                      level, steps_fwd, steps_inv);

@@ -15,6 +15,9 @@
 //
 // Footprint: about 3.3 volumes -- the image, and per level a stack plus a coefficient region of that level's size
 // (1 + 2 (1 + 1/8 + 1/64 + ...)).  Not shaved here.
+//
+// The STATIONARY volume (do_swt: pdwt_volume_create_swt) is the same handle without level plans: one device block of (3 + 8 L)
+// volumes; its fields and layout are at the end of struct pdwt_volume.
 #pragma once
 
 #include <vector>
@@ -66,4 +69,29 @@ struct pdwt_volume {
     pdwt::VolRangeTable rt_hist{}, rt_keep{};
     unsigned long long n_details = 0, n_app = 0;  // elements of the 7 L detail sub-bands, of A_L
     pdwt::VolumeWs* ops = nullptr;
+
+    // ---- the stationary volume (do_swt, pdwt_volume_create_swt): no level plans, ONE device block.  Level l = the a-trous depth
+    // pass (swt3_axis_kernels.hpp) A_{l-1} -> stack at dilation f = 2^(l-1), then one batched 2D SWT level (launch.hpp:
+    // Swt2DArgs{f, bstride = P}, batch 2 Nz) stack -> the level's four band arrays, each [2 Nz][P]: the first half of an array is
+    // the depth-low sub-band, the second half the depth-high one (A = aaa | daa, H = ada | dda, V = aad | dad, D = add | ddd: kSub).
+    // aaa of level l is A_l: the next level's depth pass reads it in place; for l < L an intermediate, for l = L coefficient 0.
+    //
+    //   block = image [Nz][P] | stack [2 Nz][P] | level 1: A H V D | ... | level L: A H V D | sums, partial sums, thresholds | slack
+    //
+    // Footprint: (3 + 8 L) volumes (1 + 2 + 4 x 2 per level) plus 256-B alignment of every buffer, the few KiB of the operators'
+    // sums and at least 16 B of slack behind everything a 2D kernel may address (the one-launch 2D kernels may read up to 12 B
+    // past the last plane).  Not shaved here.  nz / nr / nc hold (Nz, Nr, Nc) at every level: every band has the image's shape.
+    int do_swt = 0;
+    bool own_stream = false;
+    void* swt_block = nullptr;
+    real_t* swt_stack = nullptr;
+    std::vector<real_t*> swt_band;        // [4 (l - 1) + b]: band array b (0 A, 1 H, 2 V, 3 D) of level l
+    std::vector<int> width_inv;           // [l - 1]: columns per thread of level l's depth synthesis (the forward's is `width`)
+    std::vector<pdwt::BandTable> swt_bt;  // [l - 1]: the four arrays of level l as 4 bands x 2 "images" (the depth halves) of Nz P values
+    double* swt_stats = nullptr;          // [L][4][2][2]
+    double* swt_partial = nullptr;        // [L][2 * pieces of a level]
+    real_t* swt_table = nullptr;          // [L][4][2] thresholds of the last sweep
+    int swt_pieces = 0;                   // workgroups of one level's sweep
+    real_t* swt_h_table = nullptr;        // pinned: the thresholds on their way to the device
+    hipEvent_t swt_staged = nullptr;      // ... have left it
 };

@@ -1,4 +1,5 @@
-"""`Wavelets3D`: the separable decimated 3D DWT of a volume on the GPU (the pdwt_volume_* block of include/pypwt_amd.h).
+"""`Wavelets3D`: the separable 3D DWT of a volume on the GPU, decimated or -- ``do_swt=1`` -- stationary (the pdwt_volume_* block
+of include/pypwt_amd.h).
 
 The reference stops at two dimensions ("3D is not handled at the moment", pdwt/README.md:29); this class follows the 2D
 `Wavelets` in everything that carries over -- level clamping, state rules, thresholds, norms -- with the boundary rule of the
@@ -7,6 +8,7 @@ rest of the library (pywt's "periodization").  ctypes binding only.
     W = Wavelets3D(vol, "db2", 3); W.forward(); W.soft_threshold(10); W.inverse(); W.coeffs; W.image
     W.forward(); W.denoise("BayesShrink"); W.inverse()        # the threshold of every sub-band from the data, on the device
     W.forward(); W.keep_largest(fraction=0.05); W.inverse()   # best K-term approximation
+    W = Wavelets3D(vol, "db4", 3, do_swt=1); W.forward(); W.soft_threshold(10); W.inverse()   # translation-invariant denoising
 """
 import ctypes as C
 
@@ -31,6 +33,17 @@ def volume_layout(shape, wname, levels, lib=None):
     return nlev.value, [tuple(dims[3 * k:3 * k + 3]) for k in range(n)]
 
 
+def volume_layout_swt(shape, wname, levels, dtype=np.float32, lib=None):
+    """(levels after clamping, bytes of device memory) of a STATIONARY volume of `shape` and `dtype`: a pure host computation
+    (pdwt_volume_layout_swt), no device needed -- (3 + 8 L) volumes, so worth asking before the volume is created."""
+    lib = lib or _lib.load()
+    nz, nr, nc = (int(n) for n in shape)
+    nlev, nbytes = C.c_int(0), C.c_longlong(0)
+    check(lib.pdwt_volume_layout_swt(nz, nr, nc, wname.encode("ascii"), int(levels), C.byref(nlev), C.byref(nbytes),
+                                     np.dtype(dtype).itemsize), "volume_layout_swt", lib)
+    return nlev.value, nbytes.value
+
+
 class Wavelets3D(object):
     """3D DWT plan of one volume [Nz][Nr][Nc].
 
@@ -38,6 +51,14 @@ class Wavelets3D(object):
           (``__cuda_array_interface__``), copied device-to-device
     wname, levels : as for `Wavelets`; the levels are clamped by the reference's rule on the smallest of the three sizes
     device : device ordinal, -1 = the current one;  stream : a HIP stream handle to run on, None = a private stream
+    do_swt : 1 = the stationary (undecimated, a-trous) transform: pywt.swtn / pywt.iswtn with axes (z, y, x).  Every band then has
+          the volume's shape, any size from 2 on each axis is taken (odd ones too), and the device holds (3 + 8 levels) volumes
+          (`volume_layout_swt` tells beforehand).  ``coeffs`` keeps its shape ``[A_L, d_1, ..., d_L]``; pywt.swtn's list is,
+          coarsest level first, a dict per level that also holds 'aaa': ``[dict(d_L, aaa=A_L)] + [dict(d_l, aaa=...) for l = L-1 .. 1]``
+          where the 'aaa' of a level below L is an intermediate this class does not keep -- pywt.iswtn reads only the first
+          dict's.  The operators that choose a threshold or a sparsity from the data (`band_stats`, `estimate_sigma`,
+          `threshold_bands`, `denoise`, `select_magnitude`, `keep_largest`, `norms_device`) are not built for it and raise
+          NotImplementedError.
 
     Coefficient index ``num``: 0 = the approximation A_L, then 1 + 7 (l - 1) + k with level 1 the FINEST and k over the keys
     'aad', 'ada', 'add', 'daa', 'dad', 'dda', 'ddd' -- pywt.wavedecn's, axes (z, y, x).  ``coeffs`` is ``[A, d_1, ..., d_L]``
@@ -46,8 +67,9 @@ class Wavelets3D(object):
     _variant = "f32"
     _dtype = np.float32
 
-    def __init__(self, vol, wname, levels, device=-1, stream=None):
+    def __init__(self, vol, wname, levels, device=-1, stream=None, do_swt=0):
         self._h = None
+        self.do_swt = 1 if do_swt else 0
         self._lib = _lib.load(self._variant)
         dev = _device_array(vol, self._dtype)
         if dev is not None:
@@ -65,13 +87,16 @@ class Wavelets3D(object):
         if dev is not None:
             self._order_producer(dev, device)
         src = C.c_void_p(dev[0]) if dev is not None else _ptr(vol)
-        check(self._lib.pdwt_volume_create(src, self.shape[0], self.shape[1], self.shape[2], wname.encode("ascii"), int(levels),
-                                           0 if dev is not None else 1, int(device), C.c_void_p(stream) if stream else None,
-                                           C.byref(h)), "Wavelets3D", self._lib)
+        create = self._lib.pdwt_volume_create_swt if self.do_swt else self._lib.pdwt_volume_create
+        check(create(src, self.shape[0], self.shape[1], self.shape[2], wname.encode("ascii"), int(levels),
+                     0 if dev is not None else 1, int(device), C.c_void_p(stream) if stream else None, C.byref(h)), "Wavelets3D", self._lib)
         self._h = h
         self.levels = self.info()["nlevels"]
         self.hlen = self.info()["hlen"]
-        self._shapes = volume_layout(self.shape, wname, self.levels, self._lib)[1]
+        if self.do_swt:
+            self._shapes = [self.shape] * (1 + 7 * self.levels)
+        else:
+            self._shapes = volume_layout(self.shape, wname, self.levels, self._lib)[1]
 
     # ---- helpers
     def _check(self, rc, what=""):
@@ -109,13 +134,21 @@ class Wavelets3D(object):
     def info(self):
         v = [C.c_int() for _ in range(6)]
         self._check(self._lib.pdwt_volume_get_info(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("Nz", "Nr", "Nc", "nlevels", "hlen", "state"), (x.value for x in v)))
+        out = dict(zip(("Nz", "Nr", "Nc", "nlevels", "hlen", "state"), (x.value for x in v)))
+        out["do_swt"] = self.do_swt  # (the constructor's argument: no further call)
+        return out
 
     def __repr__(self):
-        return "<%s %s %s levels=%d>" % (type(self).__name__, "x".join(str(n) for n in self.shape), self.wname, self.levels)
+        return "<%s %s %s levels=%d%s>" % (type(self).__name__, "x".join(str(n) for n in self.shape), self.wname, self.levels,
+                                           " swt" if self.do_swt else "")
+
+    def _not_for_swt(self, method):
+        if self.do_swt:
+            raise NotImplementedError("Wavelets3D.%s is not built for stationary volumes (do_swt=1)" % method)
 
     def depth_schedule(self, level):
-        """(columns per thread, steps per depth segment forward, inverse) of the depth passes of `level` (1 .. levels)."""
+        """(columns per thread, steps per depth segment forward, inverse) of the depth passes of `level` (1 .. levels).  Stationary
+        volumes: the columns of the analysis, and the steps per segment of an orbit walk."""
         v = [C.c_int() for _ in range(3)]
         self._check(self._lib.pdwt_volume_depth_schedule(self._h, int(level), *[C.byref(x) for x in v]), "depth_schedule")
         return tuple(x.value for x in v)
@@ -279,30 +312,35 @@ class Wavelets3D(object):
     def band_stats(self, out=None):
         """(sum |c|, sum c^2) of every sub-band as float64 ON THE DEVICE: a (nbands, 2) device array -- ``out`` if given, else a
         view of the volume's own slot.  Slices and levels are pooled on the device; two calls give the same bits."""
+        self._not_for_swt("band_stats")
         arg, view = self._out(out, 2 * self.nbands, "band_stats")
         self._check(self._lib.pdwt_volume_band_stats_async(self._h, arg), "band_stats")
         return view if view is not None else self._view(self._adaptive_slots()[0], (self.nbands, 2), np.float64)
 
     def read_band_stats(self, view=None):
         """What ``band_stats`` left on the device, copied to the host (waits for the volume's stream): (nbands, 2) float64."""
+        self._not_for_swt("read_band_stats")
         return self._read(self._adaptive_slots()[0] if view is None else self._addr(view), (self.nbands, 2), np.float64)
 
     def estimate_sigma(self, skip_zeros=True, out=None):
         """The noise level sigma = median(|ddd_1|) / 0.6745 over the WHOLE finest 'ddd' sub-band (``num`` 7; the rule of
         skimage.restoration.denoise_wavelet for n-D data), as float64 ON THE DEVICE: a (1,) device array.  The median is exact;
         ``skip_zeros`` (default, as skimage does) leaves exact zeros out of it."""
+        self._not_for_swt("estimate_sigma")
         arg, view = self._out(out, 1, "estimate_sigma")
         self._check(self._lib.pdwt_volume_estimate_sigma_async(self._h, 1 if skip_zeros else 0, arg), "estimate_sigma")
         return view if view is not None else self._view(self._adaptive_slots()[1], (1,), np.float64)
 
     def read_sigma(self, view=None):
         """What ``estimate_sigma`` (or ``denoise``) left on the device, copied to the host: (1,) float64."""
+        self._not_for_swt("read_sigma")
         return self._read(self._adaptive_slots()[1] if view is None else self._addr(view), (1,), np.float64)
 
     def threshold_bands(self, betas, mode="soft"):
         """Soft or hard threshold with a threshold of its own per sub-band: ``betas`` is a (nbands,) array of the instance's dtype
         -- a numpy array or any device-array holder ``set_coeff`` accepts.  A NaN entry leaves that sub-band untouched (entry 0 is
         the approximation A_L)."""
+        self._not_for_swt("threshold_bands")
         op = self._choice(self._THRESHOLD_MODES, mode, "mode")
         dev = _device_array(betas, self._dtype)
         if dev is not None:
@@ -321,6 +359,7 @@ class Wavelets3D(object):
         ``method``: "BayesShrink" (a threshold per detail sub-band) or "VisuShrink" (sigma sqrt(2 ln(Nz Nr Nc))); ``sigma``: the
         noise level, None = ``estimate_sigma``; ``mode``: "soft" or "hard".  Nothing goes through the host; ``last_thresholds``
         shows what was applied."""
+        self._not_for_swt("denoise")
         m = self._choice(self._DENOISE_METHODS, method, "method")
         op = self._choice(self._THRESHOLD_MODES, mode, "mode")
         arg = None
@@ -334,6 +373,7 @@ class Wavelets3D(object):
     def last_thresholds(self):
         """(sigma, thresholds) of the last ``denoise``, copied to the host (waits for the volume's stream): sigma is (1,) float64,
         thresholds (nbands,) of the instance's dtype with NaN at index 0 (the approximation is left alone)."""
+        self._not_for_swt("last_thresholds")
         _, sg, tb = self._adaptive_slots()
         return self._read(sg, (1,), np.float64), self._read(tb, (self.nbands,), self._dtype)
 
@@ -366,6 +406,7 @@ class Wavelets3D(object):
         how many elements are at least that large: ``(threshold, kept)`` as device views of the volume's slots, (1,) of the
         instance's dtype and (1,) uint64.  ``fraction``: K = round(fraction * N).  Read-only; ``last_sparsify`` copies the pair to
         the host.  K = 0 gives (+inf, 0), K >= N gives (0, N)."""
+        self._not_for_swt("select_magnitude")
         kk = self._sparsify_k("select_magnitude", k, fraction, do_threshold_appcoeffs)
         self._check(self._lib.pdwt_volume_select_magnitude_async(self._h, kk, 1 if do_threshold_appcoeffs else 0, None, None), "select_magnitude")
         th, kp = self._sparsify_slots()
@@ -375,18 +416,21 @@ class Wavelets3D(object):
         """Best K-term approximation of the volume: keep, bit for bit, the K coefficients of largest magnitude (ties with the K-th
         all survive; NaNs count as larger than +inf) and set the rest to +0.0 -- the select above and one sweep over all levels,
         nothing through the host.  After ``inverse()`` it warns and does nothing, like every threshold."""
+        self._not_for_swt("keep_largest")
         kk = self._sparsify_k("keep_largest", k, fraction, do_threshold_appcoeffs)
         self._refused(self._lib.pdwt_volume_keep_largest_async(self._h, kk, 1 if do_threshold_appcoeffs else 0))
 
     def last_sparsify(self):
         """(threshold, kept) of the last ``select_magnitude`` / ``keep_largest``, copied to the host (waits for the volume's
         stream): (1,) of the instance's dtype and (1,) uint64."""
+        self._not_for_swt("last_sparsify")
         th, kp = self._sparsify_slots()
         return self._read(th, (1,), self._dtype), self._read(kp, (1,), np.uint64)
 
     def norms_device(self, out=None):
         """(sum |c|, sum c^2) over all coefficients as two float64 ON THE DEVICE, enqueued and not waited for (``norms`` blocks):
         the fixed-order sum of the ``band_stats`` rows.  Returns ``out`` if given, else a view of the volume's own slot."""
+        self._not_for_swt("norms_device")
         arg, view = self._out(out, 2, "norms_device")
         self._check(self._lib.pdwt_volume_norms_async(self._h, arg), "norms_device")
         if view is not None:
@@ -395,6 +439,7 @@ class Wavelets3D(object):
 
     def read_norms(self, view=None):
         """The two float64 a ``norms_device`` call left on the device, copied to the host (waits for the volume's stream)."""
+        self._not_for_swt("read_norms")
         addr = self._adaptive_slots()[0] + 2 * self.nbands * 8 if view is None else self._addr(view)
         res = self._read(addr, (2,), np.float64)
         return float(res[0]), float(res[1])

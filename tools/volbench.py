@@ -20,6 +20,17 @@ select_magnitude; the keep sweep's own time is (forward + keep_largest) - forwar
 
     python tools/volbench.py --ops                 > profiles/volume_opsbench.txt
 
+--swt: the STATIONARY transform (Wavelets3D(..., do_swt=1)) of 256^3 db4 and 256^3 haar, three levels: forward, inverse and forward +
+soft threshold + inverse by device events, as above.  The depth pass alone cannot be bracketed by events (it is one launch inside
+the level), so its time per level comes from a kernel trace of the same shapes, with the yardstick IN THE SAME RUN: a flat copy
+of the pass's algorithmic bytes (forward: 1 volume read + 2 written; inverse: 2 read + 1 written -- a copy of 1.5 volumes moves
+the same 3 volumes of bytes).
+
+    python tools/volbench.py --swt                                                           end-to-end times
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/volbench.py --swt --profile --case N
+    python tools/volbench.py --swt --summarize DIR --case N                                  depth pass per level against the copy
+    (the three outputs together are profiles/volume_swt_bench.txt)
+
 --profile: a short run of ONE case with one level (so that every kernel name in the trace belongs to level 1) plus the copy and
 the 2D level of the same bytes, for rocprofv3; --summarize reads the kernel trace of such a run and reports, per depth kernel,
 its share of the copy next to the share the 2D level-1 kernel reaches.
@@ -83,11 +94,11 @@ class Events(object):
         return ms.value / reps
 
 
-def make_volume(shape, wname, levels):
+def make_volume(shape, wname, levels, do_swt=0):
     from pypwt_amd import Wavelets3D
     rng = np.random.default_rng(1)
     x = (rng.random(shape, dtype=np.float32) * np.float32(255.0))
-    return Wavelets3D(x, wname, levels)
+    return Wavelets3D(x, wname, levels, do_swt=do_swt)
 
 
 def variants(W):
@@ -214,6 +225,92 @@ def run_ops(args):
         W.cleanup()
 
 
+SWT_CASES = [("256^3 db4", (256, 256, 256), "db4", 3), ("256^3 haar", (256, 256, 256), "haar", 3)]
+
+
+def run_swt(args):
+    ev = Events()
+    print("# volbench --swt: stationary 3D transform end to end, fp32, %d calls per timing after %d warm-up calls; every variant timed twice"
+          % (args.reps, args.warmup))
+    print("# %-12s %-13s %10s %10s %12s   %s" % ("case", "variant", "ms (1st)", "ms (2nd)", "Gsamples/s", "depth schedule (width, seg fwd, seg inv) per level"))
+    for k, (name, shape, wname, levels) in enumerate(SWT_CASES):
+        if args.case is not None and k != args.case:
+            continue
+        W = make_volume(shape, wname, levels, do_swt=1)
+        W.forward()
+        n = shape[0] * shape[1] * shape[2]
+        sched = [W.depth_schedule(l) for l in range(1, W.levels + 1)]
+        for vname, fn, directions in variants(W):
+            t = [ev.time(W._stream(), fn, args.reps, args.warmup) for _ in range(2)]
+            print("  %-12s %-13s %10.4f %10.4f %12.2f   %s" % (name, vname, t[0], t[1], directions * n / (min(t) * 1e6), sched))
+        W.cleanup()
+        sys.stdout.flush()
+
+
+def swt_copy_yardstick(shape, reps):
+    """A flat copy that moves the depth pass's algorithmic bytes (3 volumes): 1.5 volumes read, 1.5 written."""
+    from pypwt_amd import BatchedWavelets
+    B = BatchedWavelets(shape[0] * 3 // 2, shape[1], shape[2], "haar", 1)
+    B.fill_hash(3)
+    elems = (shape[0] * 3 // 2) * shape[1] * shape[2]
+    us = B.time_copy(elems, reps)
+    B.cleanup()
+    return elems, us
+
+
+def swt_case(args):
+    if args.case is None or not 0 <= args.case < len(SWT_CASES):
+        raise SystemExit("--swt --profile / --summarize need --case N with N in 0 .. %d: %s" % (len(SWT_CASES) - 1, [c[0] for c in SWT_CASES]))
+    return SWT_CASES[args.case]
+
+
+def run_swt_profile(args):
+    name, shape, wname, levels = swt_case(args)
+    W = make_volume(shape, wname, levels, do_swt=1)
+    vs = dict((v[0], v[1]) for v in variants(W))
+    for _ in range(args.reps):
+        vs["forward"]()
+        vs["inverse"]()
+    W.synchronize()
+    W.cleanup()
+    print("profiled", name, "stationary, levels=%d" % levels, swt_copy_yardstick(shape, args.reps))
+
+
+def run_swt_summarize(args):
+    name, shape, wname, levels = swt_case(args)
+    files = glob.glob(os.path.join(args.summarize, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        raise SystemExit("no *kernel_trace.csv under " + args.summarize)
+    rows = []
+    for f in files:
+        for row in csv.DictReader(open(f)):
+            k = re.sub(r"^void |pdwt::|\(.*$", "", row["Kernel_Name"])
+            rows.append((int(row["Start_Timestamp"]), k, (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1000.0))
+    rows.sort()
+    median = lambda v: sorted(v)[len(v) // 2]
+    copy = [d for _, k, d in rows if k.startswith("copy_kernel")]
+    if not copy:
+        raise SystemExit("no copy_kernel in the trace")
+    vol_bytes = 4.0 * shape[0] * shape[1] * shape[2]
+    print("# %s stationary, %d levels: kernel trace, median us per launch; the depth pass moves 3 volumes = %.1f MB" % (name, levels, 3 * vol_bytes / 1e6))
+    print("  %-44s %9.2f us  %7.0f GB/s" % ("copy_kernel of the same bytes (n=%d)" % len(copy), median(copy), 3 * vol_bytes / (median(copy) * 1e3)))
+    for direction in ("fwd", "inv"):
+        d = [(k, t) for _, k, t in rows if k.startswith("swt3_depth_%s_kernel" % direction)]
+        if not d or len(d) % levels:
+            raise SystemExit("expected a multiple of %d swt3_depth_%s launches, found %d" % (levels, direction, len(d)))
+        for i in range(levels):  # launches come level by level: forward 1 .. L, inverse L .. 1
+            level = i + 1 if direction == "fwd" else levels - i
+            t = [x[1] for x in d[i::levels]]
+            print("  %-44s %9.2f us  %7.0f GB/s  %.2f of the copy" % ("%s level %d (f = %d, n=%d)" % (d[i][0], level, 1 << (level - 1), len(t)), median(t),
+                                                                     3 * vol_bytes / (median(t) * 1e3), median(copy) / median(t)))
+    other = {}
+    for _, k, t in rows:
+        if not k.startswith("swt3_depth") and not k.startswith("copy_kernel"):
+            other.setdefault(k, []).append(t)
+    for k, v in sorted(other.items(), key=lambda kv: -sum(kv[1])):
+        print("  %-60s n=%4d median %9.2f us" % (k[:60], len(v), median(v)))
+
+
 def run_profile(args):
     name, shape, wname, _ = CASES[args.case]
     W = make_volume(shape, wname, 1)
@@ -259,6 +356,7 @@ def main():
     ap.add_argument("--case", type=int, default=None)
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--ops", action="store_true")
+    ap.add_argument("--swt", action="store_true")
     ap.add_argument("--summarize", default=None)
     ap.add_argument("--list", action="store_true")
     args = ap.parse_args()
@@ -266,7 +364,14 @@ def main():
         for k, c in enumerate(CASES):
             print(k, c, "bytes/sample per direction %.1f" % bytes_per_sample(c[1], c[3]))
         return
-    if args.summarize:
+    if args.swt:
+        if args.summarize:
+            run_swt_summarize(args)
+        elif args.profile:
+            run_swt_profile(args)
+        else:
+            run_swt(args)
+    elif args.summarize:
         run_summarize(args)
     elif args.profile:
         run_profile(args)
