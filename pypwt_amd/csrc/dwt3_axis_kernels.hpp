@@ -22,7 +22,7 @@
 // (tests/cpu_emu/emu_axis.cpp).
 #pragma once
 
-#include "kernels_common.hpp"
+#include "axis_common.hpp"
 #include "strip_walk.hpp"
 
 namespace pdwt {
@@ -38,11 +38,6 @@ struct Dwt3Args {
 };
 
 // ---- index math (host and device) -------------------------------------------------------------------------------------
-#ifdef PDWT_CPU_EMU
-#define PDWT_HD static inline
-#else
-#define PDWT_HD static __host__ __device__ __forceinline__
-#endif
 
 PDWT_HD int dwt3_div2(int n) { return (n + (n & 1)) / 2; }
 
@@ -72,42 +67,19 @@ PDWT_HD int dwt3_fwd_slice(int pos, int Nz) { return pos >= Nz ? Nz - 1 : pos; }
 PDWT_HD int dwt3_inv_first(int q, int hlen, int Nin) { return dwt3_true_mod(q - (hlen / 2) / 2, Nin); }
 PDWT_HD int dwt3_inv_out0(int q, int hlen) { return 2 * q - dwt3_inv_shift(hlen); }
 
-// Launch geometry, shared by the launchers (launch_dwt3.hip) and the emulation (tests/cpu_emu/emu_axis.cpp): threads per
-// workgroup; columns per thread of the wide path -- 16 B per lane up to 16 taps, 8 B from 18 taps on --; the width a launch takes
-// (the wide one where the slice length is a multiple of it and both buffers are aligned to it, else 1); column groups = gridDim.x
-constexpr int kDwt3NT = 256;
-constexpr int kDwt3TapsInLds = 18;  // from this filter length on the taps are staged in LDS, not held in scalar registers
+// Launch geometry, shared by the launchers (launch_depth3.hip) and the emulation (tests/cpu_emu/emu_axis.cpp).  Columns per thread
+// of the wide path: 16 B per lane up to 16 taps, 8 B from 18 taps on (axis_common.hpp: axis_width picks it or 1 for a launch).
 constexpr int dwt3_wide(int hlen) { return (int)(16 / sizeof(real_t)) / (hlen > 16 ? 2 : 1); }
-static inline int dwt3_width(const void* in, const void* out, long long P, int hlen) {
-    const int w = dwt3_wide(hlen);
-    const uintptr_t mask = (uintptr_t)w * sizeof(real_t) - 1;
-    const bool ok = w > 1 && P % w == 0 && !(reinterpret_cast<uintptr_t>(in) & mask) && !(reinterpret_cast<uintptr_t>(out) & mask);
-    return ok ? w : 1;
-}
-static inline long long dwt3_col_groups(long long P, int width) { return (P + (long long)kDwt3NT * width - 1) / ((long long)kDwt3NT * width); }
+// the shared geometry under this family's names, as the emulation spells it
+constexpr int kDwt3NT = kAxisNT;
+static inline int dwt3_width(const void* in, const void* out, long long P, int hlen) { return axis_width(in, out, P, dwt3_wide(hlen)); }
+static inline long long dwt3_col_groups(long long P, int width) { return axis_col_groups(P, width); }
 
 // Steps per segment: the walk of a workgroup re-reads `warm` steps' worth of history, so long segments are cheaper, but the
 // chip wants `slots` resident workgroups (strip_walk.hpp: the fewest rounds x steps per workgroup).
 static inline int dwt3_pick_seg(int steps, long long col_groups, int hlen, int slots) {
     const int warm = hlen / 2 - 1;
     return strip_walk_seg(steps, col_groups, 1, warm, slots > 0 ? slots : 1);
-}
-
-// ---- VEC columns of one slice -----------------------------------------------------------------------------------------
-
-template <int VEC>
-struct alignas(VEC * sizeof(real_t)) Dwt3Vec {
-    real_t v[VEC];
-};
-
-template <int VEC>
-PDWT_DEVICE Dwt3Vec<VEC> dwt3_load(const real_t* PDWT_RESTRICT base, long long slice, long long P, long long col) {
-    return *reinterpret_cast<const Dwt3Vec<VEC>*>(base + slice * P + col);
-}
-
-template <int VEC>
-PDWT_DEVICE void dwt3_store(real_t* PDWT_RESTRICT base, long long slice, long long P, long long col, const Dwt3Vec<VEC>& x) {
-    *reinterpret_cast<Dwt3Vec<VEC>*>(base + slice * P + col) = x;
 }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------
@@ -122,19 +94,19 @@ PDWT_DEVICE void dwt3_depth_fwd_tile(const Dwt3Args& a, const real_t* PDWT_RESTR
             const int k1 = k0 + a.seg < a.Nh ? k0 + a.seg : a.Nh;
             const int period = a.Nz + (a.Nz & 1);
             int pos = dwt3_fwd_first(k0, HLEN, a.Nz);
-            Dwt3Vec<VEC> w[HLEN];
+            AxisVec<VEC> w[HLEN];
 #pragma unroll
             for (int j = 0; j < HLEN; j++) {
-                w[j] = dwt3_load<VEC>(a.in, dwt3_fwd_slice(pos, a.Nz), a.P, col);
+                w[j] = axis_load<VEC>(a.in, dwt3_fwd_slice(pos, a.Nz), a.P, col);
                 pos = dwt3_next(pos, period);
             }
             for (int k = k0; k < k1; k++) {
                 // the two slices of the next step (periodised: always inside the input, also behind the last step)
-                const Dwt3Vec<VEC> n0 = dwt3_load<VEC>(a.in, dwt3_fwd_slice(pos, a.Nz), a.P, col);
+                const AxisVec<VEC> n0 = axis_load<VEC>(a.in, dwt3_fwd_slice(pos, a.Nz), a.P, col);
                 pos = dwt3_next(pos, period);
-                const Dwt3Vec<VEC> n1 = dwt3_load<VEC>(a.in, dwt3_fwd_slice(pos, a.Nz), a.P, col);
+                const AxisVec<VEC> n1 = axis_load<VEC>(a.in, dwt3_fwd_slice(pos, a.Nz), a.P, col);
                 pos = dwt3_next(pos, period);
-                Dwt3Vec<VEC> lo, hi;
+                AxisVec<VEC> lo, hi;
 #pragma unroll
                 for (int v = 0; v < VEC; v++) {
                     real_t aL = 0, aH = 0;
@@ -146,8 +118,8 @@ PDWT_DEVICE void dwt3_depth_fwd_tile(const Dwt3Args& a, const real_t* PDWT_RESTR
                     lo.v[v] = aL;
                     hi.v[v] = aH;
                 }
-                dwt3_store<VEC>(a.out, k, a.P, col, lo);
-                dwt3_store<VEC>(a.out, (long long)a.Nh + k, a.P, col, hi);
+                axis_store<VEC>(a.out, k, a.P, col, lo);
+                axis_store<VEC>(a.out, (long long)a.Nh + k, a.P, col, hi);
 #pragma unroll
                 for (int j = 0; j + 2 < HLEN; j++) w[j] = w[j + 2];
                 if (HLEN >= 2) {
@@ -173,18 +145,18 @@ PDWT_DEVICE void dwt3_depth_inv_tile(const Dwt3Args& a, const real_t* PDWT_RESTR
             const int q1 = q0 + a.seg < steps ? q0 + a.seg : steps;
             const int Nin = a.Nh;
             int pos = dwt3_inv_first(q0, HLEN, Nin);
-            Dwt3Vec<VEC> wa[H2], wd[H2];
+            AxisVec<VEC> wa[H2], wd[H2];
 #pragma unroll
             for (int j = 0; j < H2; j++) {
-                wa[j] = dwt3_load<VEC>(a.in, pos, a.P, col);
-                wd[j] = dwt3_load<VEC>(a.in, (long long)Nin + pos, a.P, col);
+                wa[j] = axis_load<VEC>(a.in, pos, a.P, col);
+                wd[j] = axis_load<VEC>(a.in, (long long)Nin + pos, a.P, col);
                 pos = dwt3_next(pos, Nin);
             }
             for (int q = q0; q < q1; q++) {
-                const Dwt3Vec<VEC> na = dwt3_load<VEC>(a.in, pos, a.P, col);
-                const Dwt3Vec<VEC> nd = dwt3_load<VEC>(a.in, (long long)Nin + pos, a.P, col);
+                const AxisVec<VEC> na = axis_load<VEC>(a.in, pos, a.P, col);
+                const AxisVec<VEC> nd = axis_load<VEC>(a.in, (long long)Nin + pos, a.P, col);
                 pos = dwt3_next(pos, Nin);
-                Dwt3Vec<VEC> o0, o1;
+                AxisVec<VEC> o0, o1;
 #pragma unroll
                 for (int v = 0; v < VEC; v++) {
                     real_t ra0 = 0, rd0 = 0, ra1 = 0, rd1 = 0;
@@ -199,8 +171,8 @@ PDWT_DEVICE void dwt3_depth_inv_tile(const Dwt3Args& a, const real_t* PDWT_RESTR
                     o1.v[v] = ra1 + rd1;
                 }
                 const int g0 = dwt3_inv_out0(q, HLEN);
-                if (g0 >= 0 && g0 < a.Nz) dwt3_store<VEC>(a.out, g0, a.P, col, o0);
-                if (g0 + 1 < a.Nz) dwt3_store<VEC>(a.out, g0 + 1, a.P, col, o1);
+                if (g0 >= 0 && g0 < a.Nz) axis_store<VEC>(a.out, g0, a.P, col, o0);
+                if (g0 + 1 < a.Nz) axis_store<VEC>(a.out, g0 + 1, a.P, col, o1);
 #pragma unroll
                 for (int j = 0; j + 1 < H2; j++) {
                     wa[j] = wa[j + 1];
@@ -220,26 +192,26 @@ PDWT_DEVICE void dwt3_depth_inv_tile(const Dwt3Args& a, const real_t* PDWT_RESTR
 // tap tables out of the scalar file) and the FMA loop reads them from there with uniform addresses.
 template <int HLEN, int VEC, bool INV>
 PDWT_DEVICE void dwt3_depth_run(const Dwt3Args& a) {
-    if constexpr (HLEN >= kDwt3TapsInLds) {
+    if constexpr (HLEN >= kAxisTapsInLds) {
         __shared__ real_t taps[2 * HLEN];
         if (threadIdx.x < HLEN) taps[threadIdx.x] = a.fb.lo[threadIdx.x];
         else if (threadIdx.x < 2 * HLEN) taps[threadIdx.x] = a.fb.hi[threadIdx.x - HLEN];
         __syncthreads();
-        if constexpr (INV) dwt3_depth_inv_tile<HLEN, VEC, kDwt3NT>(a, taps, taps + HLEN, (long long)blockIdx.x, (int)blockIdx.y);
-        else dwt3_depth_fwd_tile<HLEN, VEC, kDwt3NT>(a, taps, taps + HLEN, (long long)blockIdx.x, (int)blockIdx.y);
+        if constexpr (INV) dwt3_depth_inv_tile<HLEN, VEC, kAxisNT>(a, taps, taps + HLEN, (long long)blockIdx.x, (int)blockIdx.y);
+        else dwt3_depth_fwd_tile<HLEN, VEC, kAxisNT>(a, taps, taps + HLEN, (long long)blockIdx.x, (int)blockIdx.y);
     } else {
-        if constexpr (INV) dwt3_depth_inv_tile<HLEN, VEC, kDwt3NT>(a, a.fb.lo, a.fb.hi, (long long)blockIdx.x, (int)blockIdx.y);
-        else dwt3_depth_fwd_tile<HLEN, VEC, kDwt3NT>(a, a.fb.lo, a.fb.hi, (long long)blockIdx.x, (int)blockIdx.y);
+        if constexpr (INV) dwt3_depth_inv_tile<HLEN, VEC, kAxisNT>(a, a.fb.lo, a.fb.hi, (long long)blockIdx.x, (int)blockIdx.y);
+        else dwt3_depth_fwd_tile<HLEN, VEC, kAxisNT>(a, a.fb.lo, a.fb.hi, (long long)blockIdx.x, (int)blockIdx.y);
     }
 }
 
 template <int HLEN, int VEC>
-__global__ __launch_bounds__(kDwt3NT) void dwt3_depth_fwd_kernel(const Dwt3Args a) {
+__global__ __launch_bounds__(kAxisNT) void dwt3_depth_fwd_kernel(const Dwt3Args a) {
     dwt3_depth_run<HLEN, VEC, false>(a);
 }
 
 template <int HLEN, int VEC>
-__global__ __launch_bounds__(kDwt3NT) void dwt3_depth_inv_kernel(const Dwt3Args a) {
+__global__ __launch_bounds__(kAxisNT) void dwt3_depth_inv_kernel(const Dwt3Args a) {
     dwt3_depth_run<HLEN, VEC, true>(a);
 }
 #endif

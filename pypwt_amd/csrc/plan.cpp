@@ -19,6 +19,7 @@
 #include <vector>
 #include <strings.h>
 
+#include "host_util.hpp"
 #include "launch.hpp"
 #include "launch_util.hpp"
 #include "nonsep_kernels.hpp"
@@ -40,42 +41,10 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess)                                                                       \
-            return fail(PDWT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                        __LINE__);                                                                  \
-    } while (0)
-
 #define CHECK_HANDLE(h) \
     if (!(h)) return fail(PDWT_ERR_ARG, "null plan handle")
 
-int div2(int n) { return (n + (n & 1)) / 2; }  // pdwt/src/utils.cu:24-27
-
-int ilog2(int i) {  // pdwt/src/utils.cu:14-20 (terminates for i <= 0 too)
-    int l = 0;
-    while (i > 1) {
-        i >>= 1;
-        ++l;
-    }
-    return l;
-}
-
 long long pad64(long long n) { return (n + 63) & ~63LL; }
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
 
 // ---------------------------------------------------------------- device-memory / stream pool
 // The reference's users often build one Wavelets object per image (its tests and tutorials do); hipMalloc + hipFree +
@@ -1145,16 +1114,6 @@ int circshift_impl(pdwt_plan* p, int sr, int sc, int inplace) {
     return PDWT_OK;
 }
 
-// beta / sqrt(2)^levels for the approximation band (pdwt/src/common.cu:229-236)
-real_t app_beta(real_t beta, int levels, int normalize) {
-    if (normalize > 0) {
-        const int n2 = levels / 2;
-        beta /= (real_t)(1 << n2);
-        if (n2 * 2 != levels) beta = (real_t)(beta / 1.4142135623730951);
-    }
-    return beta;
-}
-
 int threshold_sweep(pdwt_plan* p, int op, real_t beta, int do_app, int normalize, const char* what);
 
 // can the inverse of this plan apply a soft threshold on the fly?  (fused 2D SWT kernels on every level)
@@ -1263,7 +1222,6 @@ int threshold_sweep(pdwt_plan* p, int op, real_t beta, int do_app, int normalize
 // them that is called.  The sweep geometry (BandTable) is fixed with the plan's layout: about 2048 workgroups over the whole
 // coefficient region for the threshold sweep (1024 for the sums, the grids of the whole-arena map and norms kernels), pieces of
 // at least 4096 values, every piece inside one (band, image).
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 int ensure_adaptive(pdwt_plan* p) {
     if (p->adaptive) return PDWT_OK;

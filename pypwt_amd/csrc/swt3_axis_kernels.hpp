@@ -24,7 +24,7 @@
 // (tests/cpu_emu/emu_swt_axis.cpp).
 #pragma once
 
-#include "kernels_common.hpp"
+#include "axis_common.hpp"
 #include "strip_walk.hpp"
 
 namespace pdwt {
@@ -43,13 +43,8 @@ struct Swt3Args {
 };
 
 // ---- index math (host and device) -------------------------------------------------------------------------------------
-#ifdef PDWT_CPU_EMU
-#define PDWT_SWT3_HD static inline
-#else
-#define PDWT_SWT3_HD static __host__ __device__ __forceinline__
-#endif
 
-PDWT_SWT3_HD int swt3_gcd(int a, int b) {
+PDWT_HD int swt3_gcd(int a, int b) {
     while (b) {
         const int t = a % b;
         a = b;
@@ -57,43 +52,39 @@ PDWT_SWT3_HD int swt3_gcd(int a, int b) {
     }
     return a;
 }
-PDWT_SWT3_HD int swt3_orbits(int f, int Nz) { return swt3_gcd(f % Nz, Nz); }  // gcd(0, Nz) = Nz: Nz | f, every slice its own orbit
-PDWT_SWT3_HD int swt3_steps(int f, int Nz) { return Nz / swt3_orbits(f, Nz); }
-PDWT_SWT3_HD int swt3_centre(int hlen, bool inverse) { return inverse ? hlen / 2 : hlen / 2 - 1; }
+PDWT_HD int swt3_orbits(int f, int Nz) { return swt3_gcd(f % Nz, Nz); }  // gcd(0, Nz) = Nz: Nz | f, every slice its own orbit
+PDWT_HD int swt3_steps(int f, int Nz) { return Nz / swt3_orbits(f, Nz); }
+PDWT_HD int swt3_centre(int hlen, bool inverse) { return inverse ? hlen / 2 : hlen / 2 - 1; }
 
 // output slice of step t of orbit o, and the first tap's source slice of an output slice g: true modulos, once per segment
-PDWT_SWT3_HD int swt3_out_slice(int o, int t, int fm, int Nz) { return (int)(((long long)o + (long long)t * fm) % Nz); }
-PDWT_SWT3_HD int swt3_first_src(int g, int c, int fm, int Nz) {
+PDWT_HD int swt3_out_slice(int o, int t, int fm, int Nz) { return (int)(((long long)o + (long long)t * fm) % Nz); }
+PDWT_HD int swt3_first_src(int g, int c, int fm, int Nz) {
     const long long m = ((long long)g - (long long)c * fm) % Nz;
     return (int)(m < 0 ? m + Nz : m);
 }
 // the next slice along the orbit (fm < Nz: one conditional subtraction)
-PDWT_SWT3_HD int swt3_next(int pos, int fm, int Nz) {
+PDWT_HD int swt3_next(int pos, int fm, int Nz) {
     const int n = pos + fm;
     return n >= Nz ? n - Nz : n;
 }
 
-// Launch geometry, shared by the launchers (launch_swt3.hip) and the emulation (tests/cpu_emu/emu_swt_axis.cpp).  Columns per
+// Launch geometry, shared by the launchers (launch_depth3.hip) and the emulation (tests/cpu_emu/emu_swt_axis.cpp).  Columns per
 // thread of the wide path: the register window is HLEN x VEC values forward and 2 HLEN x VEC inverse, so 16 B per lane up to 16
 // taps forward (8 inverse), half of that up to 40 (16 inverse), and a quarter for the inverse from 18 taps on -- never below one
 // column (fp64 reaches it earlier).  tools/spillscan.py confirms that no instantiation spills; docs/KERNELS.md has the counts.
-constexpr int kSwt3NT = 256;
-constexpr int kSwt3TapsInLds = 18;  // from this filter length on the taps are staged in LDS (dwt3_axis_kernels.hpp)
 constexpr int swt3_wide(int hlen, bool inverse) {
     const int full = (int)(16 / sizeof(real_t));
     const int div = inverse ? (hlen > 16 ? 4 : hlen > 8 ? 2 : 1) : (hlen > 16 ? 2 : 1);
     return full / div > 1 ? full / div : 1;
 }
-static inline int swt3_width(const void* in, const void* out, long long P, int hlen, bool inverse) {
-    const int w = swt3_wide(hlen, inverse);
-    const uintptr_t mask = (uintptr_t)w * sizeof(real_t) - 1;
-    const bool ok = w > 1 && P % w == 0 && !(reinterpret_cast<uintptr_t>(in) & mask) && !(reinterpret_cast<uintptr_t>(out) & mask);
-    return ok ? w : 1;
-}
-static inline long long swt3_col_groups(long long P, int width) { return (P + (long long)kSwt3NT * width - 1) / ((long long)kSwt3NT * width); }
 
 // Steps per segment of an orbit walk: a segment re-reads HLEN - 1 slices of history, the chip wants `slots` resident workgroups,
 // and the orbits are independent units beside the column groups (strip_walk.hpp: the fewest rounds x steps per workgroup).
+// the shared geometry under this family's names, as the emulation spells it
+constexpr int kSwt3NT = kAxisNT;
+static inline int swt3_width(const void* in, const void* out, long long P, int hlen, bool inverse) { return axis_width(in, out, P, swt3_wide(hlen, inverse)); }
+static inline long long swt3_col_groups(long long P, int width) { return axis_col_groups(P, width); }
+
 static inline int swt3_pick_seg(int steps, long long col_groups, int orbits, int hlen, int slots) {
     return strip_walk_seg(steps, col_groups * orbits, 1, hlen - 1, slots > 0 ? slots : 1);
 }
@@ -108,23 +99,6 @@ static inline void swt3_geometry(Swt3Args& a, int Nz, int f, int seg) {
     a.nseg = (a.steps + a.seg - 1) / a.seg;
 }
 
-// ---- VEC columns of one slice -----------------------------------------------------------------------------------------
-
-template <int VEC>
-struct alignas(VEC * sizeof(real_t)) Swt3Vec {
-    real_t v[VEC];
-};
-
-template <int VEC>
-PDWT_DEVICE Swt3Vec<VEC> swt3_load(const real_t* PDWT_RESTRICT base, long long slice, long long P, long long col) {
-    return *reinterpret_cast<const Swt3Vec<VEC>*>(base + slice * P + col);
-}
-
-template <int VEC>
-PDWT_DEVICE void swt3_store(real_t* PDWT_RESTRICT base, long long slice, long long P, long long col, const Swt3Vec<VEC>& x) {
-    *reinterpret_cast<Swt3Vec<VEC>*>(base + slice * P + col) = x;
-}
-
 // ---- forward ------------------------------------------------------------------------------------------------------------
 
 template <int HLEN, int VEC, int NT>
@@ -136,17 +110,17 @@ PDWT_DEVICE void swt3_depth_fwd_tile(const Swt3Args& a, const real_t* PDWT_RESTR
             const int t1 = t0 + a.seg < a.steps ? t0 + a.seg : a.steps;
             int g = swt3_out_slice(o, t0, a.fm, a.Nz);
             int pos = swt3_first_src(g, swt3_centre(HLEN, false), a.fm, a.Nz);
-            Swt3Vec<VEC> w[HLEN];
+            AxisVec<VEC> w[HLEN];
 #pragma unroll
             for (int j = 0; j < HLEN; j++) {
-                w[j] = swt3_load<VEC>(a.in, pos, a.P, col);
+                w[j] = axis_load<VEC>(a.in, pos, a.P, col);
                 pos = swt3_next(pos, a.fm, a.Nz);
             }
             for (int t = t0; t < t1; t++) {
                 // the slice of the next step (periodised: always inside the input, also behind the last step)
-                const Swt3Vec<VEC> n0 = swt3_load<VEC>(a.in, pos, a.P, col);
+                const AxisVec<VEC> n0 = axis_load<VEC>(a.in, pos, a.P, col);
                 pos = swt3_next(pos, a.fm, a.Nz);
-                Swt3Vec<VEC> lo, hi;
+                AxisVec<VEC> lo, hi;
 #pragma unroll
                 for (int v = 0; v < VEC; v++) {
                     real_t aL = 0, aH = 0;
@@ -158,8 +132,8 @@ PDWT_DEVICE void swt3_depth_fwd_tile(const Swt3Args& a, const real_t* PDWT_RESTR
                     lo.v[v] = aL;
                     hi.v[v] = aH;
                 }
-                swt3_store<VEC>(a.out, g, a.P, col, lo);
-                swt3_store<VEC>(a.out, (long long)a.Nz + g, a.P, col, hi);
+                axis_store<VEC>(a.out, g, a.P, col, lo);
+                axis_store<VEC>(a.out, (long long)a.Nz + g, a.P, col, hi);
                 g = swt3_next(g, a.fm, a.Nz);
 #pragma unroll
                 for (int j = 0; j + 1 < HLEN; j++) w[j] = w[j + 1];
@@ -180,18 +154,18 @@ PDWT_DEVICE void swt3_depth_inv_tile(const Swt3Args& a, const real_t* PDWT_RESTR
             const int t1 = t0 + a.seg < a.steps ? t0 + a.seg : a.steps;
             int g = swt3_out_slice(o, t0, a.fm, a.Nz);
             int pos = swt3_first_src(g, swt3_centre(HLEN, true), a.fm, a.Nz);
-            Swt3Vec<VEC> wa[HLEN], wd[HLEN];
+            AxisVec<VEC> wa[HLEN], wd[HLEN];
 #pragma unroll
             for (int j = 0; j < HLEN; j++) {
-                wa[j] = swt3_load<VEC>(a.in, pos, a.P, col);
-                wd[j] = swt3_load<VEC>(a.in, (long long)a.Nz + pos, a.P, col);
+                wa[j] = axis_load<VEC>(a.in, pos, a.P, col);
+                wd[j] = axis_load<VEC>(a.in, (long long)a.Nz + pos, a.P, col);
                 pos = swt3_next(pos, a.fm, a.Nz);
             }
             for (int t = t0; t < t1; t++) {
-                const Swt3Vec<VEC> na = swt3_load<VEC>(a.in, pos, a.P, col);
-                const Swt3Vec<VEC> nd = swt3_load<VEC>(a.in, (long long)a.Nz + pos, a.P, col);
+                const AxisVec<VEC> na = axis_load<VEC>(a.in, pos, a.P, col);
+                const AxisVec<VEC> nd = axis_load<VEC>(a.in, (long long)a.Nz + pos, a.P, col);
                 pos = swt3_next(pos, a.fm, a.Nz);
-                Swt3Vec<VEC> r;
+                AxisVec<VEC> r;
 #pragma unroll
                 for (int v = 0; v < VEC; v++) {
                     real_t ra = 0, rd = 0;
@@ -202,7 +176,7 @@ PDWT_DEVICE void swt3_depth_inv_tile(const Swt3Args& a, const real_t* PDWT_RESTR
                     }
                     r.v[v] = (real_t)0.5 * (ra + rd);
                 }
-                swt3_store<VEC>(a.out, g, a.P, col, r);
+                axis_store<VEC>(a.out, g, a.P, col, r);
                 g = swt3_next(g, a.fm, a.Nz);
 #pragma unroll
                 for (int j = 0; j + 1 < HLEN; j++) {
@@ -221,26 +195,26 @@ PDWT_DEVICE void swt3_depth_inv_tile(const Swt3Args& a, const real_t* PDWT_RESTR
 // 18 taps on staged in LDS once per workgroup and read with uniform addresses.
 template <int HLEN, int VEC, bool INV>
 PDWT_DEVICE void swt3_depth_run(const Swt3Args& a) {
-    if constexpr (HLEN >= kSwt3TapsInLds) {
+    if constexpr (HLEN >= kAxisTapsInLds) {
         __shared__ real_t taps[2 * HLEN];
         if (threadIdx.x < HLEN) taps[threadIdx.x] = a.fb.lo[threadIdx.x];
         else if (threadIdx.x < 2 * HLEN) taps[threadIdx.x] = a.fb.hi[threadIdx.x - HLEN];
         __syncthreads();
-        if constexpr (INV) swt3_depth_inv_tile<HLEN, VEC, kSwt3NT>(a, taps, taps + HLEN, (long long)blockIdx.x, (int)blockIdx.y);
-        else swt3_depth_fwd_tile<HLEN, VEC, kSwt3NT>(a, taps, taps + HLEN, (long long)blockIdx.x, (int)blockIdx.y);
+        if constexpr (INV) swt3_depth_inv_tile<HLEN, VEC, kAxisNT>(a, taps, taps + HLEN, (long long)blockIdx.x, (int)blockIdx.y);
+        else swt3_depth_fwd_tile<HLEN, VEC, kAxisNT>(a, taps, taps + HLEN, (long long)blockIdx.x, (int)blockIdx.y);
     } else {
-        if constexpr (INV) swt3_depth_inv_tile<HLEN, VEC, kSwt3NT>(a, a.fb.lo, a.fb.hi, (long long)blockIdx.x, (int)blockIdx.y);
-        else swt3_depth_fwd_tile<HLEN, VEC, kSwt3NT>(a, a.fb.lo, a.fb.hi, (long long)blockIdx.x, (int)blockIdx.y);
+        if constexpr (INV) swt3_depth_inv_tile<HLEN, VEC, kAxisNT>(a, a.fb.lo, a.fb.hi, (long long)blockIdx.x, (int)blockIdx.y);
+        else swt3_depth_fwd_tile<HLEN, VEC, kAxisNT>(a, a.fb.lo, a.fb.hi, (long long)blockIdx.x, (int)blockIdx.y);
     }
 }
 
 template <int HLEN, int VEC>
-__global__ __launch_bounds__(kSwt3NT) void swt3_depth_fwd_kernel(const Swt3Args a) {
+__global__ __launch_bounds__(kAxisNT) void swt3_depth_fwd_kernel(const Swt3Args a) {
     swt3_depth_run<HLEN, VEC, false>(a);
 }
 
 template <int HLEN, int VEC>
-__global__ __launch_bounds__(kSwt3NT) void swt3_depth_inv_kernel(const Swt3Args a) {
+__global__ __launch_bounds__(kAxisNT) void swt3_depth_inv_kernel(const Swt3Args a) {
     swt3_depth_run<HLEN, VEC, true>(a);
 }
 #endif

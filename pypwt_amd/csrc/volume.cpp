@@ -1,9 +1,12 @@
-// volume.cpp -- the pdwt_volume_* block of the C ABI (include/pypwt_amd.h): the 3D DWT of a volume as depth passes
-// (launch_dwt3.hip) around one-level batched 2D plans (volume.hpp has the layout).  The 2D side goes through the plans' own
-// entry points -- pdwt_create_batched, pdwt_forward / pdwt_inverse, pdwt_threshold_bands, pdwt_band_stats_async --, so nothing
-// a 1D or 2D plan does is restated here.  The adaptive and K-term operators pool the slices and levels of a sub-band on the device
-// (volume_ops_kernels.hpp, launch_volume_ops.hip): a volume is ONE image.  The STATIONARY volume (pdwt_volume_create_swt) has no level
-// plans: a-trous depth passes (launch_swt3.hip) around the batched 2D SWT launchers of launch.hpp, called directly, on one device block.
+// volume.cpp -- the pdwt_volume_* block of the C ABI (include/pypwt_amd.h).  A handle is one of two objects (volume.hpp):
+//   pdwt::VolumeDwt  the 3D DWT as depth passes (launch_depth3.hip) around one-level batched 2D plans.  The 2D side goes through the
+//                    plans' own entry points -- pdwt_create_batched, pdwt_forward / pdwt_inverse, pdwt_threshold_bands,
+//                    pdwt_band_stats_async --, so nothing a 1D or 2D plan does is restated here.  The adaptive and K-term operators
+//                    pool the slices and levels of a sub-band on the device (volume_ops_kernels.hpp, launch_volume_ops.hip): a
+//                    volume is ONE image.
+//   pdwt::VolumeSwt  the stationary transform: no level plans, a-trous depth passes (launch_depth3.hip) around the batched 2D SWT
+//                    launchers of launch.hpp, called directly, on one device block.
+// The entry points at the end check their arguments and the state, select the device and call the object.
 #include "volume.hpp"
 
 #include <math.h>
@@ -12,6 +15,7 @@
 
 #include <limits>
 
+#include "host_util.hpp"
 #include "launch.hpp"
 #include "wavelet_table.hpp"
 
@@ -21,52 +25,20 @@ namespace {
 
 #define VFAIL(code, ...) set_last_error((code), __VA_ARGS__)
 
-#define HIP_TRY(expr)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess)                                                                                    \
-            return VFAIL(PDWT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-#define PDWT_TRY(expr)                \
-    do {                              \
-        const int rc_ = (expr);       \
-        if (rc_ != PDWT_OK) return rc_; \
-    } while (0)
-
-int div2(int n) { return (n + (n & 1)) / 2; }
-
-int ilog2(int i) {  // pdwt/src/utils.cu:14-20
-    int l = 0;
-    while (i > 1) {
-        i >>= 1;
-        ++l;
-    }
-    return l;
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        else if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 // the seven detail sub-bands of a level in pywt.wavedecn's sorted key order, axes (z, y, x): depth half (0 low, 1 high) and
 // band of the level's 2D plan (0 A, 1 H, 2 V, 3 D)
 const struct { const char* key; int half, band; } kSub[7] = {
     {"aad", 0, 2}, {"ada", 0, 1}, {"add", 0, 3}, {"daa", 1, 0}, {"dad", 1, 2}, {"dda", 1, 1}, {"ddd", 1, 3}};
 
-// argument checks shared by create and layout; no HIP call
-int check_shape(const char* what, int Nz, int Nr, int Nc, const char* wname, const WaveletEntry** w) {
+// the per-band operators of a batched plan take at most 65535 images, and a level's plan holds 2 div2(Nz) of them
+constexpr int kMaxDepthDwt = 65534;
+// the batched 2D level of a stationary volume runs 2 Nz planes in gridDim.z
+constexpr int kMaxDepthSwt = 32767;
+
+// argument checks shared by the creates and the layouts; no HIP call
+int check_shape(const char* what, int Nz, int Nr, int Nc, const char* wname, int max_depth, const WaveletEntry** w) {
     if (Nz < 2 || Nr < 2 || Nc < 2) return VFAIL(PDWT_ERR_ARG, "%s: every axis needs at least 2 samples, got (%d, %d, %d)", what, Nz, Nr, Nc);
-    // the per-band operators of a batched plan take at most 65535 images, and a level's plan holds 2 div2(Nz) of them
-    if (Nz > 65534) return VFAIL(PDWT_ERR_ARG, "%s: depth %d is beyond the limit of 65534 slices", what, Nz);
+    if (Nz > max_depth) return VFAIL(PDWT_ERR_ARG, "%s: depth %d is beyond the limit of %d slices", what, Nz, max_depth);
     if (!wname) return VFAIL(PDWT_ERR_ARG, "%s: wname is null", what);
     *w = find_wavelet(wname);
     if (!*w) return VFAIL(PDWT_ERR_WAVELET, "unknown wavelet name %s", wname);
@@ -94,12 +66,52 @@ int clamp_levels(int Nz, int Nr, int Nc, const char* wname, int hlen, int levels
     return levels;
 }
 
-int num_bands(const pdwt_volume* v) { return 1 + 7 * v->nlevels; }
+template <typename T>  // double (the wavelet table) or real_t (a caller's bank)
+void fill_bank(pdwt_volume* v, int hlen, const T* dec_lo, const T* dec_hi, const T* rec_lo, const T* rec_hi) {
+    for (int i = 0; i < kMaxTaps; i++) {
+        const bool in = i < hlen;
+        v->dec.lo[i] = in ? (real_t)dec_lo[i] : 0, v->dec.hi[i] = in ? (real_t)dec_hi[i] : 0;
+        v->rec.lo[i] = in ? (real_t)rec_lo[i] : 0, v->rec.hi[i] = in ? (real_t)rec_hi[i] : 0;
+    }
+}
 
-struct SubBand {
-    int level, half, band;  // level 1 .. L, depth half, band of that level's plan
-    int depth, rows, cols;
-};
+// What both creates do first: the checks that need no device, the device, and a new V that knows its sizes, its levels, its name
+// and its bank and owns nothing yet.  device_id < 0 becomes the current device.
+template <class V>
+int open_volume(const char* what, int Nz, int Nr, int Nc, const char* wname, int levels, int max_depth, int& device_id,
+                pdwt_volume_handle* out, V** made) {
+    if (!out) return VFAIL(PDWT_ERR_ARG, "%s: out is null", what);
+    *out = nullptr;
+    const WaveletEntry* w = nullptr;
+    PDWT_TRY(check_shape(what, Nz, Nr, Nc, wname, max_depth, &w));
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return VFAIL(PDWT_ERR_HIP, "no HIP device available (this library has no CPU path)");
+    if (device_id < 0) HIP_TRY(hipGetDevice(&device_id));
+    if (device_id >= ndev) return VFAIL(PDWT_ERR_ARG, "device %d out of range (%d devices)", device_id, ndev);
+
+    V* v = new V();
+    v->device = device_id;
+    v->Nz = Nz, v->Nr = Nr, v->Nc = Nc;
+    v->hlen = w->hlen;
+    v->nlevels = clamp_levels(Nz, Nr, Nc, wname, w->hlen, levels, true);
+    snprintf(v->wname, sizeof(v->wname), "%s", wname);
+    fill_bank(v, w->hlen, w->dec_lo, w->dec_hi, w->rec_lo, w->rec_hi);
+    *made = v;
+    return PDWT_OK;
+}
+
+// the image a create was given (or zeros), on the volume's stream
+hipError_t upload_image(pdwt_volume* v, const pdwt_real* img, int mem_is_on_host) {
+    const size_t bytes = (size_t)v->Nz * v->Nr * v->Nc * sizeof(real_t);
+    hipError_t e = img ? hipMemcpyAsync(v->image, img, bytes, mem_is_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, v->stream)
+                       : hipMemsetAsync(v->image, 0, bytes, v->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(v->stream);
+    return e;
+}
+
+int num_bands(const pdwt_volume* v) { return 1 + 7 * v->nlevels; }
 
 bool locate(const pdwt_volume* v, int num, SubBand* s) {
     if (num < 0 || num >= num_bands(v)) return false;
@@ -118,60 +130,47 @@ bool locate(const pdwt_volume* v, int num, SubBand* s) {
     return true;
 }
 
-long long elems(const SubBand& s) { return (long long)s.depth * s.rows * s.cols; }
+const real_t kLeave = std::numeric_limits<real_t>::quiet_NaN();  // a NaN entry of a threshold table leaves that (band, image) alone
 
-real_t* sub_ptr(const pdwt_volume* v, const SubBand& s) {
-    real_t* base = reinterpret_cast<real_t*>(pdwt_coeff_ptr(v->plans[s.level - 1], s.band));
-    return base ? base + (long long)s.half * elems(s) : nullptr;
+// The thresholds of the global soft / hard threshold: b[l - 1] for the details of level l = 1 .. L -- beta, divided by sqrt 2 once
+// per level under `normalize` (plan.cpp: threshold_sweep, common.cu:244) -- and, returned, the one of A_L (kLeave when do_app is 0).
+real_t level_thresholds(real_t beta, int L, int do_app, int normalize, std::vector<real_t>* b) {
+    b->resize(L);
+    real_t x = beta;
+    for (int l = 1; l <= L; l++) {
+        if (normalize > 0) x = (real_t)(x / 1.4142135623730951);
+        (*b)[l - 1] = x;
+    }
+    return do_app ? app_beta(beta, L, normalize) : kLeave;
 }
 
-// A_l: the image for l = 0, else the depth-low half of band A of level l's plan
-real_t* approx_ptr(const pdwt_volume* v, int l) {
-    return l == 0 ? v->image : reinterpret_cast<real_t*>(pdwt_coeff_ptr(v->plans[l - 1], 0));
+// The two norms from the sums (sum |c|, sum c^2) of every (level, band, image): all details, and the depth-low half of band A at
+// the last level only, in a fixed order -- levels ascending, bands A H V D, the 2 half[l] images of a band in index order (the
+// depth-low half first) --, in double.  term(l, b, i) points at the two sums of image i of band b of level l.
+template <class Term>
+void sum_norms(int L, const int* half, Term term, double out[2]) {
+    double n1 = 0, n2 = 0;
+    for (int l = 1; l <= L; l++)
+        for (int b = 0; b < 4; b++)
+            for (int i = 0; i < 2 * half[l]; i++) {
+                if (b == 0 && i < half[l] && l != L) continue;
+                const double* s = term(l, b, i);
+                n1 += s[0];
+                n2 += s[1];
+            }
+    out[0] = n1, out[1] = n2;
 }
 
-real_t* stack_ptr(const pdwt_volume* v, int l) { return reinterpret_cast<real_t*>(pdwt_image_ptr(v->plans[l - 1])); }
+// ---------------------------------------------------------------- operators that pool slices and levels (volume_ops_kernels.hpp)
 
 // every level's plan is told that its coefficients are current: they were written in place (pypwt_amd/tiled.py:431-437)
-int mark_current(pdwt_volume* v) {
+int mark_current(VolumeDwt* v) {
     for (pdwt_handle p : v->plans) PDWT_TRY(pdwt_set_coeff(p, reinterpret_cast<const real_t*>(pdwt_coeff_ptr(p, 0)), 0, 1));
     return PDWT_OK;
 }
 
-real_t app_beta(real_t beta, int levels, int normalize) {  // plan.cpp: app_beta (pdwt/src/common.cu:229-236)
-    if (normalize > 0) {
-        const int n2 = levels / 2;
-        beta /= (real_t)(1 << n2);
-        if (n2 * 2 != levels) beta = (real_t)(beta / 1.4142135623730951);
-    }
-    return beta;
-}
-
-int threshold_impl(pdwt_volume* v, int op, real_t beta, int do_app, int normalize, const char* what) {
-    if (v->state == PDWT_INVERSE)
-        return VFAIL(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what);
-    DeviceGuard guard(v->device);
-    PDWT_TRY(mark_current(v));
-    const int L = v->nlevels;
-    const real_t leave = std::numeric_limits<real_t>::quiet_NaN();  // pdwt_threshold_bands: a NaN entry leaves that (band, image) alone
-    std::vector<real_t> table;
-    real_t b = beta;
-    for (int l = 1; l <= L; l++) {
-        if (normalize > 0) b = (real_t)(b / 1.4142135623730951);  // plan.cpp: threshold_sweep (common.cu:244)
-        const int half = v->nz[l], batch = 2 * half;
-        table.assign((size_t)4 * batch, b);
-        const real_t low_a = (l == L && do_app) ? app_beta(beta, L, normalize) : leave;
-        for (int i = 0; i < half; i++) table[i] = low_a;
-        PDWT_TRY(pdwt_threshold_bands(v->plans[l - 1], op, table.data(), 0));
-    }
-    return PDWT_OK;
-}
-
-// ---------------------------------------------------------------- operators that pool slices and levels (volume_ops_kernels.hpp)
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // the swept ranges of the K-term operators: per level bands H, V, D and the depth-high half of band A, then A_L; no HIP call
-void build_ranges(pdwt_volume* v) {
+void build_ranges(VolumeDwt* v) {
     const int L = v->nlevels;
     for (int which = 0; which < 2; which++) {
         VolRangeTable& t = which ? v->rt_keep : v->rt_hist;
@@ -190,7 +189,14 @@ void build_ranges(pdwt_volume* v) {
     }
 }
 
-int ensure_ops(pdwt_volume* v) {
+void free_ops(VolumeWs* w) {
+    if (w->block) (void)hipFree(w->block);
+    if (w->h_stage) (void)hipHostFree(w->h_stage);
+    if (w->staged) (void)hipEventDestroy(w->staged);
+    delete w;
+}
+
+int ensure_ops(VolumeDwt* v) {
     if (v->ops) return PDWT_OK;
     const int nb = num_bands(v), L = v->nlevels;
     VolumeWs* w = new VolumeWs();
@@ -218,10 +224,7 @@ int ensure_ops(pdwt_volume* v) {
     }
     if (rc != PDWT_OK) {
         (void)hipGetLastError();
-        if (w->block) (void)hipFree(w->block);
-        if (w->h_stage) (void)hipHostFree(w->h_stage);
-        if (w->staged) (void)hipEventDestroy(w->staged);
-        delete w;
+        free_ops(w);
         return rc;
     }
     char* at = static_cast<char*>(w->block);
@@ -245,8 +248,8 @@ int ensure_ops(pdwt_volume* v) {
 }
 
 // at most 8 bytes of host data (K, a noise level) to device memory on the volume's stream through the pinned staging buffer; the
-// host waits only if the previous upload has not left the buffer yet (plan.cpp: stage_upload)
-int stage_upload(pdwt_volume* v, void* d_dst, const void* h_src, size_t bytes) {
+// host waits only if the previous upload has not left the buffer yet (as plan.cpp's stage_upload does for a plan)
+int stage_upload(VolumeDwt* v, void* d_dst, const void* h_src, size_t bytes) {
     VolumeWs* w = v->ops;
     HIP_TRY(hipEventSynchronize(w->staged));
     memcpy(w->h_stage, h_src, bytes);
@@ -255,8 +258,17 @@ int stage_upload(pdwt_volume* v, void* d_dst, const void* h_src, size_t bytes) {
     return PDWT_OK;
 }
 
-// What every new entry point does first.  The read-only ones take what pdwt_volume_norms takes; the sweeps follow the thresholds.
-int enter_ops(pdwt_volume* v, const char* what, bool sweep) {
+// The decimated object behind a handle, for the operator entry points; a stationary volume has none of them yet.
+int as_dwt(pdwt_volume_handle v, const char* what, VolumeDwt** d) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->do_swt)
+        return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: the adaptive and K-term operators are not built for stationary volumes (do_swt)", what);
+    *d = static_cast<VolumeDwt*>(v);
+    return PDWT_OK;
+}
+
+// What every operator does first.  The read-only ones take what pdwt_volume_norms takes; the sweeps follow the thresholds.
+int enter_ops(VolumeDwt* v, const char* what, bool sweep) {
     if (v->state == PDWT_INVERSE)
         return sweep ? VFAIL(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what)
                      : VFAIL(PDWT_ERR_STATE, "%s: the coefficients were modified by inverse()", what);
@@ -265,7 +277,7 @@ int enter_ops(pdwt_volume* v, const char* what, bool sweep) {
 }
 
 // per-slice sums by every level's plan, then one wavefront per sub-band adds up the slices of its depth half
-int band_stats_impl(pdwt_volume* v, double* d_out) {
+int band_stats_impl(VolumeDwt* v, double* d_out) {
     for (pdwt_handle p : v->plans) PDWT_TRY(pdwt_band_stats_async(p, nullptr));
     HIP_TRY(launch_vol_stats_reduce(v->ops->levels, d_out ? d_out : v->ops->stats, v->stream));
     return PDWT_OK;
@@ -277,7 +289,7 @@ int noise_check(const pdwt_volume* v, const char* what) {
     return n >= (1LL << 32) ? VFAIL(PDWT_ERR_UNSUPPORTED, "%s: the noise band has %lld elements (the histogram bins are 32-bit)", what, n) : PDWT_OK;
 }
 
-int estimate_sigma_impl(pdwt_volume* v, int skip_zeros, double* d_out) {
+int estimate_sigma_impl(VolumeDwt* v, int skip_zeros, double* d_out) {
     VolumeWs* w = v->ops;
     const pdwt_plan* p = v->plans[0];
     const long long n = (long long)v->nz[1] * v->nr[1] * v->nc[1];
@@ -289,15 +301,15 @@ int estimate_sigma_impl(pdwt_volume* v, int skip_zeros, double* d_out) {
 }
 
 // every level's sweep with the table its plan holds in its own slot
-int sweep_levels(pdwt_volume* v, int op) {
+int sweep_levels(VolumeDwt* v, int op) {
     for (int l = 1; l <= v->nlevels; l++) PDWT_TRY(pdwt_threshold_bands(v->plans[l - 1], op, v->ops->levels.table[l - 1], 1));
     return PDWT_OK;
 }
 
 // N: the swept elements; refused before anything is launched when the 32-bit histogram bins could overflow
-unsigned long long swept(const pdwt_volume* v, int do_app) { return v->n_details + (do_app ? v->n_app : 0); }
+unsigned long long swept(const VolumeDwt* v, int do_app) { return v->n_details + (do_app ? v->n_app : 0); }
 
-int sparsify_check(const pdwt_volume* v, const char* what, long long k, int do_app) {
+int sparsify_check(const VolumeDwt* v, const char* what, long long k, int do_app) {
     if (k < 0) return VFAIL(PDWT_ERR_ARG, "%s: K = %lld is negative", what, k);
     if (swept(v, do_app) >= (1ULL << 32))
         return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: %llu swept elements (the histogram bins are 32-bit)", what, swept(v, do_app));
@@ -306,7 +318,7 @@ int sparsify_check(const pdwt_volume* v, const char* what, long long k, int do_a
 
 // the K-th largest |c| over the detail sub-bands (and A_L): the passes of plan.cpp's select_magnitude_impl for ONE image whose
 // pieces lie in every level's arena
-int select_magnitude_impl(pdwt_volume* v, long long k, int do_app, real_t* d_threshold, unsigned long long* d_kept) {
+int select_magnitude_impl(VolumeDwt* v, long long k, int do_app, real_t* d_threshold, unsigned long long* d_kept) {
     VolumeWs* w = v->ops;
     const unsigned long long n = swept(v, do_app);
     PDWT_TRY(stage_upload(v, w->sp_k, &k, sizeof(k)));
@@ -315,19 +327,6 @@ int select_magnitude_impl(pdwt_volume* v, long long k, int do_app, real_t* d_thr
         HIP_TRY(launch_select_walk_rank(1, pass, w->sp_k, n, w->sel_state, w->sel_hist, w->sp_key, d_threshold ? d_threshold : w->sp_threshold,
                                         d_kept ? d_kept : w->sp_kept, v->stream));
     }
-    return PDWT_OK;
-}
-
-
-// ---------------------------------------------------------------- the stationary volume (volume.hpp: do_swt)
-int check_shape_swt(const char* what, int Nz, int Nr, int Nc, const char* wname, const WaveletEntry** w) {
-    if (Nz < 2 || Nr < 2 || Nc < 2) return VFAIL(PDWT_ERR_ARG, "%s: every axis needs at least 2 samples, got (%d, %d, %d)", what, Nz, Nr, Nc);
-    // the batched 2D level runs 2 Nz planes in gridDim.z
-    if (Nz > 32767) return VFAIL(PDWT_ERR_ARG, "%s: depth %d is beyond the limit of 32767 slices", what, Nz);
-    if (!wname) return VFAIL(PDWT_ERR_ARG, "%s: wname is null", what);
-    *w = find_wavelet(wname);
-    if (!*w) return VFAIL(PDWT_ERR_WAVELET, "unknown wavelet name %s", wname);
-    if ((*w)->hlen & 1) return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: filters of odd length are not built for volumes", what);
     return PDWT_OK;
 }
 
@@ -357,247 +356,227 @@ SwtLayout swt_layout(int Nz, int Nr, int Nc, int L, size_t real_bytes) {
     return y;
 }
 
-real_t* swt_sub_ptr(const pdwt_volume* v, const SubBand& s) {
-    return v->swt_band[4 * (s.level - 1) + s.band] + (long long)s.half * elems(s);
-}
+}  // namespace
 
-real_t* swt_approx_ptr(const pdwt_volume* v, int l) { return l == 0 ? v->image : v->swt_band[4 * (l - 1)]; }
-
-// host <-> device copies on the volume's stream, as pdwt_copy does for a plan (kind 0 d2d, 1 h2d, 2 d2h)
-int swt_copy(pdwt_volume* v, void* dst, const void* src, long long count, int kind) {
-    if (count == 0) return PDWT_OK;
-    const hipMemcpyKind k = kind == 0 ? hipMemcpyDeviceToDevice : (kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
-    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)count * sizeof(real_t), k, v->stream));
-    if (kind != 0) HIP_TRY(hipStreamSynchronize(v->stream));
+// ---------------------------------------------------------------- the common part
+int pdwt_volume::set_filters(int n, const real_t* dec_lo, const real_t* dec_hi, const real_t* rec_lo, const real_t* rec_hi) {
+    fill_bank(this, n, dec_lo, dec_hi, rec_lo, rec_hi);
     return PDWT_OK;
 }
 
-Swt2DArgs swt_level_args(const pdwt_volume* v, int l, bool inverse) {
+// ---------------------------------------------------------------- the decimated volume
+namespace pdwt {
+
+VolumeDwt::~VolumeDwt() {
+    if (!plans.empty()) (void)hipStreamSynchronize(stream);
+    if (ops) free_ops(ops);
+    for (size_t i = plans.size(); i-- > 0;) pdwt_destroy(plans[i]);  // plans[0] may own the stream: last
+    if (image) (void)hipFree(image);
+}
+
+real_t* VolumeDwt::sub_ptr(const SubBand& s) const {
+    real_t* base = reinterpret_cast<real_t*>(pdwt_coeff_ptr(plans[s.level - 1], s.band));
+    return base ? base + (long long)s.half * s.elems() : nullptr;
+}
+
+// A_l: the image for l = 0, else the depth-low half of band A of level l's plan
+real_t* VolumeDwt::approx_ptr(int l) const { return l == 0 ? image : reinterpret_cast<real_t*>(pdwt_coeff_ptr(plans[l - 1], 0)); }
+
+real_t* VolumeDwt::stack_ptr(int l) const { return reinterpret_cast<real_t*>(pdwt_image_ptr(plans[l - 1])); }
+
+int VolumeDwt::copy(void* dst, const void* src, long long count, int kind) { return pdwt_copy(plans[0], dst, src, count, kind); }
+
+int VolumeDwt::walk_steps(int level, bool inverse) const { return dwt3_depth_steps(nz[level - 1], hlen, inverse); }
+
+int VolumeDwt::forward_levels() {
+    for (int l = 1; l <= nlevels; l++) {
+        pdwt_handle p = plans[l - 1];
+        real_t* st = stack_ptr(l);
+        const long long P = (long long)nr[l - 1] * nc[l - 1];
+        const hipError_t e = launch_dwt3_depth_fwd(approx_ptr(l - 1), st, nz[l - 1], P, hlen, dec, seg_fwd[l - 1], stream);
+        if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "depth analysis of level %d failed: %s", l, hipGetErrorString(e));
+        PDWT_TRY(pdwt_set_image(p, st, 1));  // written in place: nothing is copied
+        PDWT_TRY(pdwt_forward(p));
+    }
+    return PDWT_OK;
+}
+
+int VolumeDwt::inverse_levels() {
+    for (int l = nlevels; l >= 1; l--) {
+        pdwt_handle p = plans[l - 1];
+        // band A's depth-low half was written in place: by the level below, by the forward or by set_coeff
+        PDWT_TRY(pdwt_set_coeff(p, reinterpret_cast<const real_t*>(pdwt_coeff_ptr(p, 0)), 0, 1));
+        PDWT_TRY(pdwt_inverse(p));
+        const long long P = (long long)nr[l - 1] * nc[l - 1];
+        const hipError_t e = launch_dwt3_depth_inv(stack_ptr(l), approx_ptr(l - 1), nz[l - 1], P, hlen, rec, seg_inv[l - 1], stream);
+        if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "depth synthesis of level %d failed: %s", l, hipGetErrorString(e));
+    }
+    return PDWT_OK;
+}
+
+// every plan's table is [band][image]: the level's threshold everywhere but on the depth-low half of band A
+int VolumeDwt::threshold(int op, const real_t* level_betas, real_t app_beta_or_nan, const char*) {
+    PDWT_TRY(mark_current(this));
+    std::vector<real_t> table;
+    for (int l = 1; l <= nlevels; l++) {
+        const int half = nz[l], batch = 2 * half;
+        table.assign((size_t)4 * batch, level_betas[l - 1]);
+        const real_t low_a = l == nlevels ? app_beta_or_nan : kLeave;  // A_L, or an intermediate
+        for (int i = 0; i < half; i++) table[i] = low_a;
+        PDWT_TRY(pdwt_threshold_bands(plans[l - 1], op, table.data(), 0));
+    }
+    return PDWT_OK;
+}
+
+int VolumeDwt::norms(double out[2]) {
+    const int L = nlevels;
+    std::vector<std::vector<double>> sums(L);  // [l - 1]: [band][image][2]
+    for (int l = 1; l <= L; l++) {
+        pdwt_handle p = plans[l - 1];
+        double* d_stats = nullptr;
+        PDWT_TRY(pdwt_band_stats_async(p, nullptr));
+        PDWT_TRY(pdwt_adaptive_slots(p, &d_stats, nullptr, nullptr));
+        sums[l - 1].resize((size_t)4 * 2 * nz[l] * 2);
+        HIP_TRY(hipMemcpyAsync(sums[l - 1].data(), d_stats, sums[l - 1].size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    sum_norms(L, nz.data(), [&](int l, int b, int i) { return &sums[l - 1][((size_t)b * 2 * nz[l] + i) * 2]; }, out);
+    return PDWT_OK;
+}
+
+int VolumeDwt::set_filters(int n, const real_t* dec_lo, const real_t* dec_hi, const real_t* rec_lo, const real_t* rec_hi) {
+    // the level plans first: a plan that refuses leaves the volume's own bank as it was
+    for (pdwt_handle p : plans) {
+        PDWT_TRY(pdwt_set_filters_forward(p, nullptr, (unsigned)n, dec_lo, dec_hi, nullptr, nullptr));
+        PDWT_TRY(pdwt_set_filters_inverse(p, rec_lo, rec_hi, nullptr, nullptr));
+    }
+    return pdwt_volume::set_filters(n, dec_lo, dec_hi, rec_lo, rec_hi);
+}
+
+// ---------------------------------------------------------------- the stationary volume
+VolumeSwt::~VolumeSwt() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (block) (void)hipFree(block);
+    if (h_table) (void)hipHostFree(h_table);
+    if (staged) (void)hipEventDestroy(staged);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+}
+
+real_t* VolumeSwt::sub_ptr(const SubBand& s) const { return band[4 * (s.level - 1) + s.band] + (long long)s.half * s.elems(); }
+
+real_t* VolumeSwt::approx_ptr(int l) const { return l == 0 ? image : band[4 * (l - 1)]; }
+
+// as pdwt_copy does for a plan
+int VolumeSwt::copy(void* dst, const void* src, long long count, int kind) {
+    if (count == 0) return PDWT_OK;
+    const hipMemcpyKind k = kind == 0 ? hipMemcpyDeviceToDevice : (kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
+    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)count * sizeof(real_t), k, stream));
+    if (kind != 0) HIP_TRY(hipStreamSynchronize(stream));
+    return PDWT_OK;
+}
+
+// the steps of one orbit walk at the level's dilation, the same in both directions
+int VolumeSwt::walk_steps(int level, bool) const { return swt3_depth_steps(Nz, 1 << (level - 1)); }
+
+Swt2DArgs VolumeSwt::level_args(int l, bool inverse) const {
     Swt2DArgs a;
-    real_t* const* b = &v->swt_band[4 * (l - 1)];
-    a.in = inverse ? nullptr : v->swt_stack;
+    real_t* const* b = &band[4 * (l - 1)];
+    a.in = inverse ? nullptr : stack;
     a.A = b[0], a.H = b[1], a.V = b[2], a.D = b[3];
-    a.out = inverse ? v->swt_stack : nullptr;
-    a.Nr = v->Nr, a.Nc = v->Nc, a.f = 1 << (l - 1);
-    a.bstride = (long long)v->Nr * v->Nc;
-    a.hlen = v->hlen;
+    a.out = inverse ? stack : nullptr;
+    a.Nr = Nr, a.Nc = Nc, a.f = 1 << (l - 1);
+    a.bstride = (long long)Nr * Nc;
+    a.hlen = hlen;
     a.soft_beta = 0;
-    a.fb = inverse ? v->rec : v->dec;
+    a.fb = inverse ? rec : dec;
     return a;
 }
 
-int swt_forward(pdwt_volume* v) {
-    const long long P = (long long)v->Nr * v->Nc;
-    const int B = 2 * v->Nz;
-    for (int l = 1; l <= v->nlevels; l++) {
-        hipError_t e = launch_swt3_depth_fwd(swt_approx_ptr(v, l - 1), v->swt_stack, v->Nz, P, 1 << (l - 1), v->hlen, v->dec, v->seg_fwd[l - 1], v->stream);
+int VolumeSwt::forward_levels() {
+    const long long P = (long long)Nr * Nc;
+    const int B = 2 * Nz;
+    for (int l = 1; l <= nlevels; l++) {
+        hipError_t e = launch_swt3_depth_fwd(approx_ptr(l - 1), stack, Nz, P, 1 << (l - 1), hlen, dec, seg_fwd[l - 1], stream);
         if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "depth analysis of level %d failed: %s", l, hipGetErrorString(e));
-        const Swt2DArgs a = swt_level_args(v, l, false);
+        const Swt2DArgs a = level_args(l, false);
         // the one-launch level first (plan.cpp: fwd_level_2d); hipErrorNotSupported is a decline
-        e = swt2_fwd_stream_takes(a, B) ? try_launch_swt2_fwd_stream(a, B, v->stream) : hipErrorNotSupported;
-        if (e == hipErrorNotSupported) e = launch_swt2_fwd(a, B, v->stream);
+        e = swt2_fwd_stream_takes(a, B) ? try_launch_swt2_fwd_stream(a, B, stream) : hipErrorNotSupported;
+        if (e == hipErrorNotSupported) e = launch_swt2_fwd(a, B, stream);
         if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "2D analysis of level %d failed: %s", l, hipGetErrorString(e));
     }
     return PDWT_OK;
 }
 
-int swt_inverse(pdwt_volume* v) {
-    const long long P = (long long)v->Nr * v->Nc;
-    const int B = 2 * v->Nz;
-    for (int l = v->nlevels; l >= 1; l--) {
-        const Swt2DArgs a = swt_level_args(v, l, true);
-        hipError_t e = swt2_inv_stream_takes(a, B) ? try_launch_swt2_inv_stream(a, B, v->stream) : hipErrorNotSupported;
-        if (e == hipErrorNotSupported) e = launch_swt2_inv(a, B, v->stream);
+int VolumeSwt::inverse_levels() {
+    const long long P = (long long)Nr * Nc;
+    const int B = 2 * Nz;
+    for (int l = nlevels; l >= 1; l--) {
+        const Swt2DArgs a = level_args(l, true);
+        hipError_t e = swt2_inv_stream_takes(a, B) ? try_launch_swt2_inv_stream(a, B, stream) : hipErrorNotSupported;
+        if (e == hipErrorNotSupported) e = launch_swt2_inv(a, B, stream);
         if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "2D synthesis of level %d failed: %s", l, hipGetErrorString(e));
-        e = launch_swt3_depth_inv(v->swt_stack, swt_approx_ptr(v, l - 1), v->Nz, P, 1 << (l - 1), v->hlen, v->rec, v->seg_inv[l - 1], v->stream);
+        e = launch_swt3_depth_inv(stack, approx_ptr(l - 1), Nz, P, 1 << (l - 1), hlen, rec, seg_inv[l - 1], stream);
         if (e != hipSuccess) return VFAIL(PDWT_ERR_HIP, "depth synthesis of level %d failed: %s", l, hipGetErrorString(e));
     }
     return PDWT_OK;
 }
 
 // the sweeps see a level as 4 bands x 2 "images" of Nz P values; bands of 2^31 values and more are beyond their index math
-int swt_ops_check(const pdwt_volume* v, const char* what) {
-    if ((long long)v->Nz * v->Nr * v->Nc >= (1LL << 31))
-        return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: sub-bands of %lld elements are beyond the operators' limit of 2^31 - 1", what, (long long)v->Nz * v->Nr * v->Nc);
+int VolumeSwt::ops_check(const char* what) const {
+    if ((long long)Nz * Nr * Nc >= (1LL << 31))
+        return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: sub-bands of %lld elements are beyond the operators' limit of 2^31 - 1", what, (long long)Nz * Nr * Nc);
     return PDWT_OK;
 }
 
-int swt_threshold(pdwt_volume* v, int op, real_t beta, int do_app, int normalize, const char* what) {
+int VolumeSwt::threshold(int op, const real_t* level_betas, real_t app_beta_or_nan, const char* what) {
+    PDWT_TRY(ops_check(what));
+    const int L = nlevels;
+    HIP_TRY(hipEventSynchronize(staged));  // the previous table has left the pinned buffer
+    for (int l = 1; l <= L; l++) {
+        for (int k = 0; k < 8; k++) h_table[8 * (l - 1) + k] = level_betas[l - 1];
+        h_table[8 * (l - 1)] = l == L ? app_beta_or_nan : kLeave;  // aaa: A_L, or an intermediate
+    }
+    HIP_TRY(hipMemcpyAsync(table, h_table, (size_t)8 * L * sizeof(real_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(staged, stream));
+    for (int l = 1; l <= L; l++)
+        HIP_TRY(launch_threshold_bands(op, reinterpret_cast<real_t*>(block), bt[l - 1], table + 8 * (l - 1), stream));
+    return PDWT_OK;
+}
+
+int VolumeSwt::norms(double out[2]) {
+    PDWT_TRY(ops_check("norms"));
+    const int L = nlevels;
+    for (int l = 1; l <= L; l++)
+        HIP_TRY(launch_band_stats(reinterpret_cast<const real_t*>(block), bt[l - 1], partial + (size_t)2 * pieces * (l - 1), stats + 16 * (l - 1), stream));
+    std::vector<double> sums((size_t)16 * L);  // [level][band][half][2]
+    HIP_TRY(hipMemcpyAsync(sums.data(), stats, sums.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const std::vector<int> one(L + 1, 1);  // a depth half is one "image"
+    sum_norms(L, one.data(), [&](int l, int b, int i) { return &sums[(size_t)16 * (l - 1) + 2 * (2 * b + i)]; }, out);
+    return PDWT_OK;
+}
+
+}  // namespace pdwt
+
+namespace {
+
+// the global soft / hard threshold of either volume
+int threshold_entry(pdwt_volume_handle v, int op, real_t beta, int do_app, int normalize, const char* what) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
     if (v->state == PDWT_INVERSE)
         return VFAIL(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what);
-    PDWT_TRY(swt_ops_check(v, what));
     DeviceGuard guard(v->device);
-    const int L = v->nlevels;
-    const real_t leave = std::numeric_limits<real_t>::quiet_NaN();  // launch_threshold_bands: a NaN entry leaves that pair alone
-    HIP_TRY(hipEventSynchronize(v->swt_staged));  // the previous table has left the pinned buffer
-    real_t* table = v->swt_h_table;
-    real_t b = beta;
-    for (int l = 1; l <= L; l++) {
-        if (normalize > 0) b = (real_t)(b / 1.4142135623730951);  // plan.cpp: threshold_sweep (common.cu:244)
-        for (int k = 0; k < 8; k++) table[8 * (l - 1) + k] = b;
-        table[8 * (l - 1)] = (l == L && do_app) ? app_beta(beta, L, normalize) : leave;  // aaa: A_L, or an intermediate
-    }
-    HIP_TRY(hipMemcpyAsync(v->swt_table, table, (size_t)8 * L * sizeof(real_t), hipMemcpyHostToDevice, v->stream));
-    HIP_TRY(hipEventRecord(v->swt_staged, v->stream));
-    for (int l = 1; l <= L; l++)
-        HIP_TRY(launch_threshold_bands(op, reinterpret_cast<real_t*>(v->swt_block), v->swt_bt[l - 1], v->swt_table + 8 * (l - 1), v->stream));
+    std::vector<real_t> level_betas;
+    const real_t a = level_thresholds(beta, v->nlevels, do_app, normalize, &level_betas);
+    return v->threshold(op, level_betas.data(), a, what);
+}
+
+// data into a sub-band or the image: nothing moves where the caller passes the destination itself
+int copy_in(pdwt_volume_handle v, real_t* dst, const pdwt_real* src, long long count, int mem_is_on_device) {
+    if (mem_is_on_device && src == dst) return PDWT_OK;
+    PDWT_TRY(v->copy(dst, src, count, mem_is_on_device ? 0 : 1));
+    if (mem_is_on_device) HIP_TRY(hipStreamSynchronize(v->stream));  // like pdwt_set_image: the source may be reused at once
     return PDWT_OK;
-}
-
-int swt_norms(pdwt_volume* v, double out[2]) {
-    if (v->state == PDWT_INVERSE) return VFAIL(PDWT_ERR_STATE, "norms: the coefficients were modified by inverse()");
-    PDWT_TRY(swt_ops_check(v, "norms"));
-    DeviceGuard guard(v->device);
-    const int L = v->nlevels;
-    for (int l = 1; l <= L; l++)
-        HIP_TRY(launch_band_stats(reinterpret_cast<const real_t*>(v->swt_block), v->swt_bt[l - 1], v->swt_partial + (size_t)2 * v->swt_pieces * (l - 1),
-                                  v->swt_stats + 16 * (l - 1), v->stream));
-    std::vector<double> sums((size_t)16 * L);
-    HIP_TRY(hipMemcpyAsync(sums.data(), v->swt_stats, sums.size() * sizeof(double), hipMemcpyDeviceToHost, v->stream));
-    HIP_TRY(hipStreamSynchronize(v->stream));
-    // [level][band][half][2]: all details, and aaa at the last level only, in a fixed order, in double
-    double n1 = 0, n2 = 0;
-    for (int l = 1; l <= L; l++)
-        for (int k = 0; k < 8; k++) {
-            if (k == 0 && l != L) continue;
-            n1 += sums[(size_t)16 * (l - 1) + 2 * k];
-            n2 += sums[(size_t)16 * (l - 1) + 2 * k + 1];
-        }
-    out[0] = n1, out[1] = n2;
-    return PDWT_OK;
-}
-
-void destroy(pdwt_volume* v);
-
-int swt_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host, int device_id, void* hip_stream,
-               pdwt_volume_handle* out) {
-    const char* what = "pdwt_volume_create_swt";
-    if (!out) return VFAIL(PDWT_ERR_ARG, "%s: out is null", what);
-    *out = nullptr;
-    const WaveletEntry* w = nullptr;
-    PDWT_TRY(check_shape_swt(what, Nz, Nr, Nc, wname, &w));
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return VFAIL(PDWT_ERR_HIP, "no HIP device available (this library has no CPU path)");
-    if (device_id < 0) HIP_TRY(hipGetDevice(&device_id));
-    if (device_id >= ndev) return VFAIL(PDWT_ERR_ARG, "device %d out of range (%d devices)", device_id, ndev);
-
-    pdwt_volume* v = new pdwt_volume();
-    v->do_swt = 1;
-    v->device = device_id;
-    v->Nz = Nz, v->Nr = Nr, v->Nc = Nc;
-    v->hlen = w->hlen;
-    v->nlevels = clamp_levels(Nz, Nr, Nc, wname, w->hlen, levels, true);
-    snprintf(v->wname, sizeof(v->wname), "%s", wname);
-    for (int i = 0; i < kMaxTaps; i++) {
-        const bool in = i < w->hlen;
-        v->dec.lo[i] = in ? (real_t)w->dec_lo[i] : 0, v->dec.hi[i] = in ? (real_t)w->dec_hi[i] : 0;
-        v->rec.lo[i] = in ? (real_t)w->rec_lo[i] : 0, v->rec.hi[i] = in ? (real_t)w->rec_hi[i] : 0;
-    }
-    DeviceGuard guard(device_id);
-    auto bail = [&](int code) {
-        destroy(v);
-        return code;
-    };
-    const int L = v->nlevels;
-    v->nz.assign(L + 1, Nz), v->nr.assign(L + 1, Nr), v->nc.assign(L + 1, Nc);
-    if (hip_stream) {
-        v->stream = (hipStream_t)hip_stream;
-    } else {
-        const hipError_t e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            v->stream = nullptr;
-            VFAIL(PDWT_ERR_HIP, "%s: hipStreamCreate: %s", what, hipGetErrorString(e));
-            return bail(PDWT_ERR_HIP);
-        }
-        v->own_stream = true;
-    }
-    const SwtLayout y = swt_layout(Nz, Nr, Nc, L, sizeof(real_t));
-    hipError_t e = hipMalloc(&v->swt_block, y.total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        v->swt_block = nullptr;
-        VFAIL(PDWT_ERR_NOMEM, "%s: hipMalloc of %zu bytes failed: %s", what, y.total, hipGetErrorString(e));
-        return bail(PDWT_ERR_NOMEM);
-    }
-    char* base = static_cast<char*>(v->swt_block);
-    v->image = reinterpret_cast<real_t*>(base + y.image);
-    v->swt_stack = reinterpret_cast<real_t*>(base + y.stack);
-    for (int k = 0; k < 4 * L; k++) v->swt_band.push_back(reinterpret_cast<real_t*>(base + y.bands + (size_t)k * y.band));
-    v->swt_stats = reinterpret_cast<double*>(base + y.stats);
-    v->swt_partial = reinterpret_cast<double*>(base + y.partial);
-    v->swt_table = reinterpret_cast<real_t*>(base + y.table);
-    v->swt_pieces = y.pieces;
-    const long long n = (long long)Nz * Nr * Nc;
-    for (int l = 1; l <= L; l++) {
-        BandTable t{};
-        t.nbands = 4;
-        t.batch = 2;
-        t.chunk = y.chunk;
-        for (int b = 0; b < 4; b++) {
-            t.off[b] = (long long)((y.bands + (size_t)(4 * (l - 1) + b) * y.band) / sizeof(real_t));
-            t.n[b] = n;
-            t.blk[b] = b * (y.pieces / 4);
-        }
-        t.blk[4] = y.pieces;
-        v->swt_bt.push_back(t);
-    }
-    const size_t bytes = (size_t)n * sizeof(real_t);
-    // everything behind the image starts as zeros: coefficients that were never computed read as 0, like a plan's arena
-    e = hipMemsetAsync(base + y.stack, 0, y.total - y.stack, v->stream);
-    if (e == hipSuccess)
-        e = img ? hipMemcpyAsync(v->image, img, bytes, mem_is_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, v->stream)
-                : hipMemsetAsync(v->image, 0, bytes, v->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(v->stream);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&v->swt_h_table, (size_t)8 * L * sizeof(real_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->swt_staged, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        VFAIL(PDWT_ERR_HIP, "%s: image upload failed: %s", what, hipGetErrorString(e));
-        return bail(PDWT_ERR_HIP);
-    }
-    // orbit segments: fixed with the layout (every buffer is 256-B aligned, so the widths depend on the plane size only)
-    const long long P = (long long)Nr * Nc;
-    for (int l = 1; l <= L; l++) {
-        const int f = 1 << (l - 1);
-        const int wf = swt3_depth_width(swt_approx_ptr(v, l - 1), v->swt_stack, P, v->hlen, false);
-        const int wi = swt3_depth_width(v->swt_stack, swt_approx_ptr(v, l - 1), P, v->hlen, true);
-        v->width.push_back(wf);
-        v->width_inv.push_back(wi);
-        v->seg_fwd.push_back(swt3_depth_seg(Nz, f, P, v->hlen, wf, swt3_depth_slots(v->hlen, wf, false)));
-        v->seg_inv.push_back(swt3_depth_seg(Nz, f, P, v->hlen, wi, swt3_depth_slots(v->hlen, wi, true)));
-    }
-    v->seg_fwd_chosen = v->seg_fwd, v->seg_inv_chosen = v->seg_inv;
-    *out = v;
-    return PDWT_OK;
-}
-
-int swt_unsupported(const char* what) {
-    return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: the adaptive and K-term operators are not built for stationary volumes (do_swt)", what);
-}
-
-void destroy(pdwt_volume* v) {
-    DeviceGuard guard(v->device);
-    if (v->do_swt) {
-        if (v->stream) (void)hipStreamSynchronize(v->stream);
-        if (v->swt_block) (void)hipFree(v->swt_block);
-        if (v->swt_h_table) (void)hipHostFree(v->swt_h_table);
-        if (v->swt_staged) (void)hipEventDestroy(v->swt_staged);
-        if (v->own_stream && v->stream) (void)hipStreamDestroy(v->stream);
-        delete v;
-        return;
-    }
-    if (!v->plans.empty()) (void)hipStreamSynchronize(v->stream);
-    if (VolumeWs* w = v->ops) {
-        if (w->block) (void)hipFree(w->block);
-        if (w->h_stage) (void)hipHostFree(w->h_stage);
-        if (w->staged) (void)hipEventDestroy(w->staged);
-        delete w;
-    }
-    for (size_t i = v->plans.size(); i-- > 0;) pdwt_destroy(v->plans[i]);  // plans[0] may own the stream: last
-    if (v->image) (void)hipFree(v->image);
-    delete v;
 }
 
 }  // namespace
@@ -607,7 +586,7 @@ extern "C" {
 
 int pdwt_volume_layout(int Nz, int Nr, int Nc, const char* wname, int levels, int* nlevels, int* dims, int capacity) {
     const WaveletEntry* w = nullptr;
-    PDWT_TRY(check_shape("pdwt_volume_layout", Nz, Nr, Nc, wname, &w));
+    PDWT_TRY(check_shape("pdwt_volume_layout", Nz, Nr, Nc, wname, kMaxDepthDwt, &w));
     const int L = clamp_levels(Nz, Nr, Nc, wname, w->hlen, levels, false);
     if (nlevels) *nlevels = L;
     int z = Nz, r = Nr, c = Nc;
@@ -624,31 +603,12 @@ int pdwt_volume_layout(int Nz, int Nr, int Nc, const char* wname, int levels, in
 
 int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host,
                        int device_id, void* hip_stream, pdwt_volume_handle* out) {
-    if (!out) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_create: out is null");
-    *out = nullptr;
-    const WaveletEntry* w = nullptr;
-    PDWT_TRY(check_shape("pdwt_volume_create", Nz, Nr, Nc, wname, &w));
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return VFAIL(PDWT_ERR_HIP, "no HIP device available (this library has no CPU path)");
-    if (device_id < 0) HIP_TRY(hipGetDevice(&device_id));
-    if (device_id >= ndev) return VFAIL(PDWT_ERR_ARG, "device %d out of range (%d devices)", device_id, ndev);
-
-    pdwt_volume* v = new pdwt_volume();
-    v->device = device_id;
-    v->Nz = Nz, v->Nr = Nr, v->Nc = Nc;
-    v->hlen = w->hlen;
-    v->nlevels = clamp_levels(Nz, Nr, Nc, wname, w->hlen, levels, true);
-    snprintf(v->wname, sizeof(v->wname), "%s", wname);
-    for (int i = 0; i < kMaxTaps; i++) {
-        const bool in = i < w->hlen;
-        v->dec.lo[i] = in ? (real_t)w->dec_lo[i] : 0, v->dec.hi[i] = in ? (real_t)w->dec_hi[i] : 0;
-        v->rec.lo[i] = in ? (real_t)w->rec_lo[i] : 0, v->rec.hi[i] = in ? (real_t)w->rec_hi[i] : 0;
-    }
+    const char* what = "pdwt_volume_create";
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(open_volume(what, Nz, Nr, Nc, wname, levels, kMaxDepthDwt, device_id, out, &v));
     DeviceGuard guard(device_id);
     auto bail = [&](int code) {
-        destroy(v);
+        delete v;
         return code;
     };
     const int L = v->nlevels;
@@ -669,21 +629,19 @@ int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char*
     hipError_t e = hipMalloc((void**)&v->image, bytes);
     if (e != hipSuccess) {
         v->image = nullptr;
-        VFAIL(PDWT_ERR_NOMEM, "pdwt_volume_create: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+        VFAIL(PDWT_ERR_NOMEM, "%s: hipMalloc of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
         return bail(PDWT_ERR_NOMEM);
     }
-    e = img ? hipMemcpyAsync(v->image, img, bytes, mem_is_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, v->stream)
-            : hipMemsetAsync(v->image, 0, bytes, v->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(v->stream);
+    e = upload_image(v, img, mem_is_on_host);
     if (e != hipSuccess) {
-        VFAIL(PDWT_ERR_HIP, "pdwt_volume_create: image upload failed: %s", hipGetErrorString(e));
+        VFAIL(PDWT_ERR_HIP, "%s: image upload failed: %s", what, hipGetErrorString(e));
         return bail(PDWT_ERR_HIP);
     }
     // depth segments: fixed with the layout (every buffer is 256-B aligned, so the width depends on the plane size only); the
     // chooser aims at the workgroups the chip keeps resident of THAT kernel (2 per CU at 40 taps, 8 for short filters)
     for (int l = 1; l <= L; l++) {
         const long long P = (long long)v->nr[l - 1] * v->nc[l - 1];
-        const int width = dwt3_depth_width(approx_ptr(v, l - 1), stack_ptr(v, l), P, v->hlen);
+        const int width = dwt3_depth_width(v->approx_ptr(l - 1), v->stack_ptr(l), P, v->hlen);
         v->width.push_back(width);
         v->seg_fwd.push_back(dwt3_depth_seg(v->nz[l - 1], P, v->hlen, width, false, dwt3_depth_slots(v->hlen, width, false)));
         v->seg_inv.push_back(dwt3_depth_seg(v->nz[l - 1], P, v->hlen, width, true, dwt3_depth_slots(v->hlen, width, true)));
@@ -695,14 +653,88 @@ int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char*
 
 int pdwt_volume_create_swt(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host,
                            int device_id, void* hip_stream, pdwt_volume_handle* out) {
-    return swt_create(img, Nz, Nr, Nc, wname, levels, mem_is_on_host, device_id, hip_stream, out);
+    const char* what = "pdwt_volume_create_swt";
+    VolumeSwt* v = nullptr;
+    PDWT_TRY(open_volume(what, Nz, Nr, Nc, wname, levels, kMaxDepthSwt, device_id, out, &v));
+    DeviceGuard guard(device_id);
+    auto bail = [&](int code) {
+        delete v;
+        return code;
+    };
+    const int L = v->nlevels;
+    v->nz.assign(L + 1, Nz), v->nr.assign(L + 1, Nr), v->nc.assign(L + 1, Nc);
+    if (hip_stream) {
+        v->stream = (hipStream_t)hip_stream;
+    } else {
+        const hipError_t e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            v->stream = nullptr;
+            VFAIL(PDWT_ERR_HIP, "%s: hipStreamCreate: %s", what, hipGetErrorString(e));
+            return bail(PDWT_ERR_HIP);
+        }
+        v->own_stream = true;
+    }
+    const SwtLayout y = swt_layout(Nz, Nr, Nc, L, sizeof(real_t));
+    hipError_t e = hipMalloc(&v->block, y.total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        v->block = nullptr;
+        VFAIL(PDWT_ERR_NOMEM, "%s: hipMalloc of %zu bytes failed: %s", what, y.total, hipGetErrorString(e));
+        return bail(PDWT_ERR_NOMEM);
+    }
+    char* base = static_cast<char*>(v->block);
+    v->image = reinterpret_cast<real_t*>(base + y.image);
+    v->stack = reinterpret_cast<real_t*>(base + y.stack);
+    for (int k = 0; k < 4 * L; k++) v->band.push_back(reinterpret_cast<real_t*>(base + y.bands + (size_t)k * y.band));
+    v->stats = reinterpret_cast<double*>(base + y.stats);
+    v->partial = reinterpret_cast<double*>(base + y.partial);
+    v->table = reinterpret_cast<real_t*>(base + y.table);
+    v->pieces = y.pieces;
+    const long long n = (long long)Nz * Nr * Nc;
+    for (int l = 1; l <= L; l++) {
+        BandTable t{};
+        t.nbands = 4;
+        t.batch = 2;
+        t.chunk = y.chunk;
+        for (int b = 0; b < 4; b++) {
+            t.off[b] = (long long)((y.bands + (size_t)(4 * (l - 1) + b) * y.band) / sizeof(real_t));
+            t.n[b] = n;
+            t.blk[b] = b * (y.pieces / 4);
+        }
+        t.blk[4] = y.pieces;
+        v->bt.push_back(t);
+    }
+    // everything behind the image starts as zeros: coefficients that were never computed read as 0, like a plan's arena
+    e = hipMemsetAsync(base + y.stack, 0, y.total - y.stack, v->stream);
+    if (e == hipSuccess) e = upload_image(v, img, mem_is_on_host);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&v->h_table, (size_t)8 * L * sizeof(real_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->staged, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        VFAIL(PDWT_ERR_HIP, "%s: image upload failed: %s", what, hipGetErrorString(e));
+        return bail(PDWT_ERR_HIP);
+    }
+    // orbit segments: fixed with the layout (every buffer is 256-B aligned, so the widths depend on the plane size only)
+    const long long P = (long long)Nr * Nc;
+    for (int l = 1; l <= L; l++) {
+        const int f = 1 << (l - 1);
+        const int wf = swt3_depth_width(v->approx_ptr(l - 1), v->stack, P, v->hlen, false);
+        const int wi = swt3_depth_width(v->stack, v->approx_ptr(l - 1), P, v->hlen, true);
+        v->width.push_back(wf);
+        v->width_inv.push_back(wi);
+        v->seg_fwd.push_back(swt3_depth_seg(Nz, f, P, v->hlen, wf, swt3_depth_slots(v->hlen, wf, false)));
+        v->seg_inv.push_back(swt3_depth_seg(Nz, f, P, v->hlen, wi, swt3_depth_slots(v->hlen, wi, true)));
+    }
+    v->seg_fwd_chosen = v->seg_fwd, v->seg_inv_chosen = v->seg_inv;
+    *out = v;
+    return PDWT_OK;
 }
 
 int pdwt_volume_is_swt(pdwt_volume_handle v) { return v ? v->do_swt : VFAIL(PDWT_ERR_ARG, "null volume handle"); }
 
 int pdwt_volume_layout_swt(int Nz, int Nr, int Nc, const char* wname, int levels, int* nlevels, long long* device_bytes, int sizeof_real) {
     const WaveletEntry* w = nullptr;
-    PDWT_TRY(check_shape_swt("pdwt_volume_layout_swt", Nz, Nr, Nc, wname, &w));
+    PDWT_TRY(check_shape("pdwt_volume_layout_swt", Nz, Nr, Nc, wname, kMaxDepthSwt, &w));
     if (sizeof_real != 0 && sizeof_real != 4 && sizeof_real != 8)
         return VFAIL(PDWT_ERR_ARG, "pdwt_volume_layout_swt: sizeof_real must be 4, 8 or 0 (this library's), got %d", sizeof_real);
     const int L = clamp_levels(Nz, Nr, Nc, wname, w->hlen, levels, false);
@@ -713,33 +745,17 @@ int pdwt_volume_layout_swt(int Nz, int Nr, int Nc, const char* wname, int levels
 
 int pdwt_volume_destroy(pdwt_volume_handle v) {
     if (!v) return PDWT_OK;
-    destroy(v);
+    DeviceGuard guard(v->device);
+    delete v;
     return PDWT_OK;
 }
 
 int pdwt_volume_forward(pdwt_volume_handle v) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
     DeviceGuard guard(v->device);
-    if (v->do_swt) {
-        const int rc = swt_forward(v);
-        v->state = rc == PDWT_OK ? PDWT_FORWARD : PDWT_FORWARD_ERROR;
-        return rc;
-    }
-    for (int l = 1; l <= v->nlevels; l++) {
-        pdwt_handle p = v->plans[l - 1];
-        real_t* stack = stack_ptr(v, l);
-        const long long P = (long long)v->nr[l - 1] * v->nc[l - 1];
-        const hipError_t e = launch_dwt3_depth_fwd(approx_ptr(v, l - 1), stack, v->nz[l - 1], P, v->hlen, v->dec, v->seg_fwd[l - 1], v->stream);
-        int rc = e == hipSuccess ? PDWT_OK : VFAIL(PDWT_ERR_HIP, "depth analysis of level %d failed: %s", l, hipGetErrorString(e));
-        if (rc == PDWT_OK) rc = pdwt_set_image(p, stack, 1);  // written in place: nothing is copied
-        if (rc == PDWT_OK) rc = pdwt_forward(p);
-        if (rc != PDWT_OK) {
-            v->state = PDWT_FORWARD_ERROR;
-            return rc;
-        }
-    }
-    v->state = PDWT_FORWARD;
-    return PDWT_OK;
+    const int rc = v->forward_levels();
+    v->state = rc == PDWT_OK ? PDWT_FORWARD : PDWT_FORWARD_ERROR;
+    return rc;
 }
 
 int pdwt_volume_inverse(pdwt_volume_handle v) {
@@ -749,28 +765,9 @@ int pdwt_volume_inverse(pdwt_volume_handle v) {
     if (v->state == PDWT_FORWARD_ERROR || v->state == PDWT_THRESHOLD_ERROR || v->state == PDWT_CREATION_ERROR)
         return VFAIL(PDWT_ERR_STATE, "inverse transform not computed, as there was an error in a previous stage");
     DeviceGuard guard(v->device);
-    if (v->do_swt) {
-        const int rc = swt_inverse(v);
-        v->state = rc == PDWT_OK ? PDWT_INVERSE : PDWT_INVERSE_ERROR;
-        return rc;
-    }
-    for (int l = v->nlevels; l >= 1; l--) {
-        pdwt_handle p = v->plans[l - 1];
-        // band A's depth-low half was written in place: by the level below, by the forward or by set_coeff
-        int rc = pdwt_set_coeff(p, reinterpret_cast<const real_t*>(pdwt_coeff_ptr(p, 0)), 0, 1);
-        if (rc == PDWT_OK) rc = pdwt_inverse(p);
-        if (rc == PDWT_OK) {
-            const long long P = (long long)v->nr[l - 1] * v->nc[l - 1];
-            const hipError_t e = launch_dwt3_depth_inv(stack_ptr(v, l), approx_ptr(v, l - 1), v->nz[l - 1], P, v->hlen, v->rec, v->seg_inv[l - 1], v->stream);
-            if (e != hipSuccess) rc = VFAIL(PDWT_ERR_HIP, "depth synthesis of level %d failed: %s", l, hipGetErrorString(e));
-        }
-        if (rc != PDWT_OK) {
-            v->state = PDWT_INVERSE_ERROR;
-            return rc;
-        }
-    }
-    v->state = PDWT_INVERSE;
-    return PDWT_OK;
+    const int rc = v->inverse_levels();
+    v->state = rc == PDWT_OK ? PDWT_INVERSE : PDWT_INVERSE_ERROR;
+    return rc;
 }
 
 int pdwt_volume_get_info(pdwt_volume_handle v, int* Nz, int* Nr, int* Nc, int* nlevels, int* hlen, int* state) {
@@ -788,20 +785,14 @@ long long pdwt_volume_get_image(pdwt_volume_handle v, pdwt_real* dst) {
     if (!v || !dst) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_get_image: null argument");
     DeviceGuard guard(v->device);
     const long long n = (long long)v->Nz * v->Nr * v->Nc;
-    if (v->do_swt) PDWT_TRY(swt_copy(v, dst, v->image, n, 2));
-    else PDWT_TRY(pdwt_copy(v->plans[0], dst, v->image, n, 2));
+    PDWT_TRY(v->copy(dst, v->image, n, 2));
     return n;
 }
 
 int pdwt_volume_set_image(pdwt_volume_handle v, const pdwt_real* src, int mem_is_on_device) {
     if (!v || !src) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_set_image: null argument");
     DeviceGuard guard(v->device);
-    const long long n = (long long)v->Nz * v->Nr * v->Nc;
-    if (!(mem_is_on_device && src == v->image)) {
-        if (v->do_swt) PDWT_TRY(swt_copy(v, v->image, src, n, mem_is_on_device ? 0 : 1));
-        else PDWT_TRY(pdwt_copy(v->plans[0], v->image, src, n, mem_is_on_device ? 0 : 1));
-        if (mem_is_on_device) HIP_TRY(hipStreamSynchronize(v->stream));  // like pdwt_set_image: the source may be reused at once
-    }
+    PDWT_TRY(copy_in(v, v->image, src, (long long)v->Nz * v->Nr * v->Nc, mem_is_on_device));
     v->state = PDWT_INIT;
     return PDWT_OK;
 }
@@ -813,7 +804,7 @@ long long pdwt_volume_coeff_count(pdwt_volume_handle v, int num, int* depth, int
     if (depth) *depth = s.depth;
     if (rows) *rows = s.rows;
     if (cols) *cols = s.cols;
-    return elems(s);
+    return s.elems();
 }
 
 long long pdwt_volume_get_coeff(pdwt_volume_handle v, pdwt_real* dst, int num) {
@@ -825,9 +816,8 @@ long long pdwt_volume_get_coeff(pdwt_volume_handle v, pdwt_real* dst, int num) {
         return 0;
     }
     DeviceGuard guard(v->device);
-    if (v->do_swt) PDWT_TRY(swt_copy(v, dst, swt_sub_ptr(v, s), elems(s), 2));
-    else PDWT_TRY(pdwt_copy(v->plans[s.level - 1], dst, sub_ptr(v, s), elems(s), 2));
-    return elems(s);
+    PDWT_TRY(v->copy(dst, v->sub_ptr(s), s.elems(), 2));
+    return s.elems();
 }
 
 int pdwt_volume_set_coeff(pdwt_volume_handle v, const pdwt_real* src, int num, int mem_is_on_device) {
@@ -835,12 +825,7 @@ int pdwt_volume_set_coeff(pdwt_volume_handle v, const pdwt_real* src, int num, i
     SubBand s;
     if (!locate(v, num, &s)) return VFAIL(PDWT_ERR_ARG, "coefficient index %d out of range", num);
     DeviceGuard guard(v->device);
-    real_t* dst = v->do_swt ? swt_sub_ptr(v, s) : sub_ptr(v, s);
-    if (!(mem_is_on_device && src == dst)) {
-        if (v->do_swt) PDWT_TRY(swt_copy(v, dst, src, elems(s), mem_is_on_device ? 0 : 1));
-        else PDWT_TRY(pdwt_copy(v->plans[s.level - 1], dst, src, elems(s), mem_is_on_device ? 0 : 1));
-        if (mem_is_on_device) HIP_TRY(hipStreamSynchronize(v->stream));
-    }
+    PDWT_TRY(copy_in(v, v->sub_ptr(s), src, s.elems(), mem_is_on_device));
     // as pdwt_set_coeff: once the approximation has been supplied again the coefficients are current
     if (num == 0 && v->state == PDWT_INVERSE) v->state = PDWT_FORWARD;
     return PDWT_OK;
@@ -852,65 +837,36 @@ intptr_t pdwt_volume_coeff_ptr(pdwt_volume_handle v, int num) {
     SubBand s;
     if (!v || !locate(v, num, &s)) return 0;
     DeviceGuard guard(v->device);
-    return (intptr_t)(v->do_swt ? swt_sub_ptr(v, s) : sub_ptr(v, s));
+    return (intptr_t)v->sub_ptr(s);
 }
 
 int pdwt_volume_soft_threshold(pdwt_volume_handle v, pdwt_real beta, int do_thresh_appcoeffs, int normalize) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_threshold(v, EW_SOFT, beta, do_thresh_appcoeffs, normalize, "soft_threshold");
-    return threshold_impl(v, EW_SOFT, beta, do_thresh_appcoeffs, normalize, "soft_threshold");
+    return threshold_entry(v, EW_SOFT, beta, do_thresh_appcoeffs, normalize, "soft_threshold");
 }
 
 int pdwt_volume_hard_threshold(pdwt_volume_handle v, pdwt_real beta, int do_thresh_appcoeffs, int normalize) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_threshold(v, EW_HARD, beta, do_thresh_appcoeffs, normalize, "hard_threshold");
-    return threshold_impl(v, EW_HARD, beta, do_thresh_appcoeffs, normalize, "hard_threshold");
+    return threshold_entry(v, EW_HARD, beta, do_thresh_appcoeffs, normalize, "hard_threshold");
 }
 
 int pdwt_volume_norms(pdwt_volume_handle v, double out[2]) {
     if (!v || !out) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_norms: null argument");
-    if (v->do_swt) return swt_norms(v, out);
-    if (v->state == PDWT_INVERSE)
-        return VFAIL(PDWT_ERR_STATE, "norms: the coefficients were modified by inverse()");
+    if (v->state == PDWT_INVERSE) return VFAIL(PDWT_ERR_STATE, "norms: the coefficients were modified by inverse()");
     DeviceGuard guard(v->device);
-    const int L = v->nlevels;
-    std::vector<std::vector<double>> sums(L);
-    for (int l = 1; l <= L; l++) {
-        pdwt_handle p = v->plans[l - 1];
-        double* d_stats = nullptr;
-        PDWT_TRY(pdwt_band_stats_async(p, nullptr));
-        PDWT_TRY(pdwt_adaptive_slots(p, &d_stats, nullptr, nullptr));
-        sums[l - 1].resize((size_t)4 * 2 * v->nz[l] * 2);
-        HIP_TRY(hipMemcpyAsync(sums[l - 1].data(), d_stats, sums[l - 1].size() * sizeof(double), hipMemcpyDeviceToHost, v->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(v->stream));
-    // all details, and the depth-low half of band A at the last level only; [band][image][2], in a fixed order, in double
-    double n1 = 0, n2 = 0;
-    for (int l = 1; l <= L; l++) {
-        const int half = v->nz[l], batch = 2 * half;
-        for (int b = 0; b < 4; b++)
-            for (int i = 0; i < batch; i++) {
-                if (b == 0 && i < half && l != L) continue;
-                n1 += sums[l - 1][((size_t)b * batch + i) * 2];
-                n2 += sums[l - 1][((size_t)b * batch + i) * 2 + 1];
-            }
-    }
-    out[0] = n1, out[1] = n2;
-    return PDWT_OK;
+    return v->norms(out);
 }
 
-// ---------------------------------------------------------------- NEW: the adaptive and K-term operators on ONE volume
-int pdwt_volume_band_stats_async(pdwt_volume_handle v, double* d_out) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_band_stats_async");
+// ---------------------------------------------------------------- the adaptive and K-term operators on ONE (decimated) volume
+int pdwt_volume_band_stats_async(pdwt_volume_handle h, double* d_out) {
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_band_stats_async", &v));
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "band_stats", false));
     return band_stats_impl(v, d_out);
 }
 
-int pdwt_volume_norms_async(pdwt_volume_handle v, double* d_out2) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_norms_async");
+int pdwt_volume_norms_async(pdwt_volume_handle h, double* d_out2) {
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_norms_async", &v));
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "norms", false));
     PDWT_TRY(band_stats_impl(v, nullptr));
@@ -918,18 +874,18 @@ int pdwt_volume_norms_async(pdwt_volume_handle v, double* d_out2) {
     return PDWT_OK;
 }
 
-int pdwt_volume_estimate_sigma_async(pdwt_volume_handle v, int skip_zeros, double* d_out) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_estimate_sigma_async");
+int pdwt_volume_estimate_sigma_async(pdwt_volume_handle h, int skip_zeros, double* d_out) {
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_estimate_sigma_async", &v));
     DeviceGuard guard(v->device);
     PDWT_TRY(noise_check(v, "estimate_sigma"));
     PDWT_TRY(enter_ops(v, "estimate_sigma", false));
     return estimate_sigma_impl(v, skip_zeros, d_out);
 }
 
-int pdwt_volume_threshold_bands(pdwt_volume_handle v, int op, const pdwt_real* table, int table_on_device) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_threshold_bands");
+int pdwt_volume_threshold_bands(pdwt_volume_handle h, int op, const pdwt_real* table, int table_on_device) {
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_threshold_bands", &v));
     if (!table) return VFAIL(PDWT_ERR_ARG, "threshold_bands: null table");
     if (op != EW_SOFT && op != EW_HARD) return VFAIL(PDWT_ERR_ARG, "threshold_bands: op must be 0 (soft) or 1 (hard)");
     DeviceGuard guard(v->device);
@@ -946,16 +902,16 @@ int pdwt_volume_threshold_bands(pdwt_volume_handle v, int op, const pdwt_real* t
         for (int b = 0; b < 4; b++)
             for (int i = 0; i < batch; i++) {
                 const int num = vol_num_of(l, v->nlevels, b, i, half);
-                per[(size_t)b * batch + i] = num < 0 ? std::numeric_limits<real_t>::quiet_NaN() : table[num];
+                per[(size_t)b * batch + i] = num < 0 ? kLeave : table[num];
             }
         PDWT_TRY(pdwt_threshold_bands(v->plans[l - 1], op, per.data(), 0));
     }
     return PDWT_OK;
 }
 
-int pdwt_volume_denoise_async(pdwt_volume_handle v, int method, int op, const double* sigma, int skip_zeros) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_denoise_async");
+int pdwt_volume_denoise_async(pdwt_volume_handle h, int method, int op, const double* sigma, int skip_zeros) {
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_denoise_async", &v));
     if (method != PDWT_DENOISE_BAYES && method != PDWT_DENOISE_VISU) return VFAIL(PDWT_ERR_ARG, "denoise: unknown method %d", method);
     if (op != EW_SOFT && op != EW_HARD) return VFAIL(PDWT_ERR_ARG, "denoise: op must be 0 (soft) or 1 (hard)");
     if (!sigma) PDWT_TRY(noise_check(v, "denoise"));
@@ -971,9 +927,9 @@ int pdwt_volume_denoise_async(pdwt_volume_handle v, int method, int op, const do
     return sweep_levels(v, op);
 }
 
-int pdwt_volume_adaptive_slots(pdwt_volume_handle v, double** d_stats, double** d_sigma, pdwt_real** d_table) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_adaptive_slots");
+int pdwt_volume_adaptive_slots(pdwt_volume_handle h, double** d_stats, double** d_sigma, pdwt_real** d_table) {
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_adaptive_slots", &v));
     DeviceGuard guard(v->device);
     PDWT_TRY(ensure_ops(v));
     if (d_stats) *d_stats = v->ops->stats;
@@ -982,19 +938,19 @@ int pdwt_volume_adaptive_slots(pdwt_volume_handle v, double** d_stats, double** 
     return PDWT_OK;
 }
 
-int pdwt_volume_select_magnitude_async(pdwt_volume_handle v, long long k, int do_thresh_appcoeffs, pdwt_real* d_threshold,
+int pdwt_volume_select_magnitude_async(pdwt_volume_handle h, long long k, int do_thresh_appcoeffs, pdwt_real* d_threshold,
                                        unsigned long long* d_kept) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_select_magnitude_async");
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_select_magnitude_async", &v));
     PDWT_TRY(sparsify_check(v, "select_magnitude", k, do_thresh_appcoeffs));
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "select_magnitude", false));
     return select_magnitude_impl(v, k, do_thresh_appcoeffs, d_threshold, d_kept);
 }
 
-int pdwt_volume_keep_largest_async(pdwt_volume_handle v, long long k, int do_thresh_appcoeffs) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_keep_largest_async");
+int pdwt_volume_keep_largest_async(pdwt_volume_handle h, long long k, int do_thresh_appcoeffs) {
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_keep_largest_async", &v));
     PDWT_TRY(sparsify_check(v, "keep_largest", k, do_thresh_appcoeffs));
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "keep_largest", true));
@@ -1003,9 +959,9 @@ int pdwt_volume_keep_largest_async(pdwt_volume_handle v, long long k, int do_thr
     return PDWT_OK;
 }
 
-int pdwt_volume_sparsify_slots(pdwt_volume_handle v, pdwt_real** d_threshold, unsigned long long** d_kept) {
-    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
-    if (v->do_swt) return swt_unsupported("pdwt_volume_sparsify_slots");
+int pdwt_volume_sparsify_slots(pdwt_volume_handle h, pdwt_real** d_threshold, unsigned long long** d_kept) {
+    VolumeDwt* v = nullptr;
+    PDWT_TRY(as_dwt(h, "pdwt_volume_sparsify_slots", &v));
     DeviceGuard guard(v->device);
     PDWT_TRY(ensure_ops(v));
     if (d_threshold) *d_threshold = v->ops->sp_threshold;
@@ -1047,25 +1003,13 @@ int pdwt_volume_set_filters(pdwt_volume_handle v, int hlen, const pdwt_real* dec
     if (hlen != v->hlen)
         return VFAIL(PDWT_ERR_ARG, "pdwt_volume_set_filters: %d taps, the volume was created with %d (the schedule is not rebuilt)", hlen, v->hlen);
     DeviceGuard guard(v->device);
-    // the level plans first: a plan that refuses leaves the volume's own bank as it was (a stationary volume has none)
-    for (pdwt_handle p : v->plans) {
-        PDWT_TRY(pdwt_set_filters_forward(p, nullptr, (unsigned)hlen, dec_lo, dec_hi, nullptr, nullptr));
-        PDWT_TRY(pdwt_set_filters_inverse(p, rec_lo, rec_hi, nullptr, nullptr));
-    }
-    for (int i = 0; i < kMaxTaps; i++) {
-        const bool in = i < hlen;
-        v->dec.lo[i] = in ? dec_lo[i] : 0, v->dec.hi[i] = in ? dec_hi[i] : 0;
-        v->rec.lo[i] = in ? rec_lo[i] : 0, v->rec.hi[i] = in ? rec_hi[i] : 0;
-    }
-    return PDWT_OK;
+    return v->set_filters(hlen, dec_lo, dec_hi, rec_lo, rec_hi);
 }
 
 int pdwt_volume_set_depth_segments(pdwt_volume_handle v, int level, int seg_fwd, int seg_inv) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
     if (level < 1 || level > v->nlevels) return VFAIL(PDWT_ERR_ARG, "level %d out of range (1 .. %d)", level, v->nlevels);
-    // (a stationary volume: the steps of one orbit walk at the level's dilation, the same in both directions)
-    const int steps_fwd = v->do_swt ? swt3_depth_steps(v->Nz, 1 << (level - 1)) : dwt3_depth_steps(v->nz[level - 1], v->hlen, false),
-              steps_inv = v->do_swt ? steps_fwd : dwt3_depth_steps(v->nz[level - 1], v->hlen, true);
+    const int steps_fwd = v->walk_steps(level, false), steps_inv = v->walk_steps(level, true);
     if (seg_fwd < 0 || seg_fwd > steps_fwd || seg_inv < 0 || seg_inv > steps_inv)
         return VFAIL(PDWT_ERR_ARG, "pdwt_volume_set_depth_segments: (%d, %d) steps per segment, level %d walks (%d, %d) steps", seg_fwd, seg_inv,
                      level, steps_fwd, steps_inv);

@@ -53,7 +53,7 @@ EMU_API int emu_axis_width(long long P, int hlen) {
 
 EMU_API int emu_axis_steps(int Nz, int hlen, int inverse) { return inverse ? dwt3_inv_steps(Nz, hlen) : dwt3_fwd_steps(Nz); }
 
-// the host chooser of launch_dwt3.hip for `slots` resident workgroups
+// the host chooser of launch_depth3.hip for `slots` resident workgroups
 EMU_API int emu_axis_seg(int Nz, long long P, int hlen, int width, int inverse, int slots) {
     return dwt3_pick_seg(emu_axis_steps(Nz, hlen, inverse), dwt3_col_groups(P, width), hlen, slots);
 }

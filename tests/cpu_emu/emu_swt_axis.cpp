@@ -52,7 +52,7 @@ EMU_API int emu_swt_axis_orbits(int Nz, int f) { return swt3_orbits(f, Nz); }
 
 EMU_API int emu_swt_axis_steps(int Nz, int f) { return swt3_steps(f, Nz); }
 
-// the host chooser of launch_swt3.hip for `slots` resident workgroups
+// the host chooser of launch_depth3.hip for `slots` resident workgroups
 EMU_API int emu_swt_axis_seg(int Nz, int f, long long P, int hlen, int width, int slots) {
     return swt3_pick_seg(swt3_steps(f, Nz), swt3_col_groups(P, width), swt3_orbits(f, Nz), hlen, slots);
 }

@@ -29,7 +29,7 @@ import tap_banks
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpu_emu", "emu_axis.cpp")
 CSRC = os.path.join(os.path.dirname(HERE), "pypwt_amd", "csrc")
-DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("dwt3_axis_kernels.hpp", "kernels_common.hpp", "strip_walk.hpp")]
+DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("dwt3_axis_kernels.hpp", "axis_common.hpp", "kernels_common.hpp", "strip_walk.hpp")]
 BASE = ["g++", "-O2", "-g", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wall", "-Wno-unknown-pragmas", "-DPDWT_CPU_EMU"]
 WNAME = {2: "haar", 4: "db2", 8: "db4", 16: "db8", 18: "db9", 40: "db20"}
 LENGTHS = tuple(range(2, 41, 2))  # every instantiation

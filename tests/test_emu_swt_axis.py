@@ -45,7 +45,7 @@ from test_emu_axis import BASE, CASES, LENGTHS, PLANES, SLOTS, filters_of
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpu_emu", "emu_swt_axis.cpp")
 CSRC = os.path.join(os.path.dirname(HERE), "pypwt_amd", "csrc")
-DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("swt3_axis_kernels.hpp", "kernels_common.hpp", "strip_walk.hpp")]
+DEPS = [SRC] + [os.path.join(CSRC, f) for f in ("swt3_axis_kernels.hpp", "axis_common.hpp", "kernels_common.hpp", "strip_walk.hpp")]
 DILATIONS = (1, 2, 4, 8, 16)
 SMALL_PLANES = (1, 2, 3, 4, 5)
 DEPTHS = (1, 3, 7, 16, 41)
