@@ -114,6 +114,10 @@ long long pdwt_copy_capacity(pdwt_handle h); /* the largest `elems` pdwt_time_co
  *   "wave2"          1: eligible forward level pairs run as ONE two-level wave launch (default 0: measured
  *                    slower than two launches on MI355X, kept for tests and re-measurement) */
 int pdwt_set_tuning(const char* key, int value);
+/* One more key, kept beside the table above (csrc/tuning_knobs.inc says why) -- inv_coarse3: the inverse of the three coarsest
+ * 2D DWT levels of a large plane in ONE launch (csrc/dwt2_inv_coarse_kernels.hpp; fp32 libraries, even filters of at most 8 taps).
+ * 0: never; 1 (default): where that launch writes more than 2^20 and at most 2^22 samples over the batch (the 2048^2 plane of
+ * one 4096^2 image); 2: wherever the kernel applies (tests).  Read when a plan is created, like the others. */
 
 /* Test hooks of a volume (tests/test_gpu_volume_taps.py).  Custom filter banks on volumes are NOT part of the product: these two
  * exist so that every depth-kernel instantiation can be run with a bank whose every tap counts, at every segment length.

@@ -108,6 +108,14 @@ hipError_t launch_dwt2_fwd_pyr3(const real_t* in, real_t* const det[9], real_t* 
                                 const FilterBank& fb, int batch, hipStream_t s);
 hipError_t launch_dwt2_inv_pyr3(const real_t* app, real_t* const det[9], real_t* out, int N0r, int N0c, int hlen,
                                 const FilterBank& fb, int batch, hipStream_t s);
+// the three COARSEST levels of a large plane undone in one launch (launch_dwt2_inv_coarse.hip; fp32 libraries, even filters of at
+// most 8 taps): same contract as launch_dwt2_inv_pyr3; rows a multiple of 8, columns of 32, planes that hold a tile's staged regions
+bool dwt2_inv_coarse3_supported(int hlen, int N0r, int N0c);
+hipError_t launch_dwt2_inv_coarse3(const real_t* app, real_t* const det[9], real_t* out, int N0r, int N0c, int hlen,
+                                   const FilterBank& fb, int batch, hipStream_t s);
+// pdwt_set_tuning("inv_coarse3"): 0 never, 1 the size rule of build_schedule, 2 wherever supported (tests); read when a plan is built
+int inv_coarse3_mode();
+int set_inv_coarse3_mode(int v);  // returns the previous value
 // ALL remaining levels of small approximations in one launch, one workgroup per image (launch_dwt2_tail.hip): (R0, C0) enter
 // the group's finest level (at most 16384 samples, fp64 8192; even sizes at every level's input: powers of two or not), det[3 k + b] = band b of the
 // group's k-th level (finest first); forward: in = A_{l-1}, out = A_L; inverse: in = A_L, out = A_{l-1}

@@ -55,6 +55,11 @@ hipError_t launch_dwt2_inv_strip2(const real_t* const[4], const real_t* const[3]
                                   const FilterBank&, int, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_dwt2_inv_pyr2(const real_t* const[4], const real_t* const[3], real_t*, int, int, int,
                                 const FilterBank&, int, hipStream_t) { return hipErrorNotSupported; }
+bool dwt2_inv_coarse3_supported(int, int, int) { return false; }
+hipError_t launch_dwt2_inv_coarse3(const real_t*, real_t* const[9], real_t*, int, int, int, const FilterBank&, int,
+                                   hipStream_t) { return hipErrorNotSupported; }
+int inv_coarse3_mode() { return 0; }
+int set_inv_coarse3_mode(int) { return 0; }
 // the register-ring kernels for 12-20 taps keep hlen tap pairs in SGPRs and hlen/2 x 8 running sums in VGPRs: in doubles neither fits
 // (hipcc: 256 VGPRs + 300-900 B of scratch per lane), so the fp64 library does not build them
 hipError_t try_launch_dwt2_fwd_ring(const Fwd2DArgs&, int, hipStream_t, int, int) { return hipErrorNotSupported; }

@@ -369,6 +369,7 @@ int create_impl(const real_t* img, int batch, int Nr, int Nc, const char* wname,
     }
     if ((rc = build_layout(p)) != PDWT_OK) return bail(rc);
     p->tune = current_tuning();
+    p->inv_coarse3 = inv_coarse3_mode();
     build_schedule(p);
     if (img) {
         hipError_t e = hipMemcpyAsync(p->image(), img, (size_t)batch * Nr * Nc * sizeof(real_t),
@@ -462,6 +463,16 @@ void build_schedule(pdwt_plan* p) {
             const long long per_image = 1LL << (short_whole ? tune::pyr3_image_short_log2 : (hlen <= 8 ? tune::pyr3_image_log2 : tune::pyr3_image_long_log2));
             return fusable && !no_pyr3 && left >= 3 && left != 4 && samples(l) <= (1LL << tune::pyr3_max_log2) &&
                    (long long)p->lr[l - 1] * p->lc[l - 1] <= per_image && dwt2_pyr3_supported(hlen, p->lr[l - 1], p->lc[l - 1]);
+        };
+        // The INVERSE of the three coarsest levels [L-2, L] of a LARGE plane in one launch (dwt2_inv_coarse_kernels.hpp): where the
+        // launch writes more than the small pyramid's limit and at most 2^22 samples over the batch -- the 2048^2 plane under the
+        // level-1 launch of one 4096^2 image, whose two coarse launches (tile pyramid + level tile) are latency chains, not
+        // bandwidth: 14.6 -> 11.4 us, the step of cfg2 71.4 -> 68.6 us (profiles/r07_inv_coarse3_ab.txt).  Forward: never (its halo
+        // compounds).  "inv_coarse3" key: 0 never, 2 wherever the kernel applies (tests).
+        auto coarse3_at = [&](int l, bool inverse) {
+            if (!inverse || !fusable || no_pyr || p->inv_coarse3 == 0 || l < 1 || l != L - 2 || hlen > 8) return false;
+            const bool sized = samples(l) > (1LL << tune::inv_coarse3_above_log2) && samples(l) <= (1LL << tune::inv_coarse3_max_log2);
+            return (sized || p->inv_coarse3 >= 2) && dwt2_inv_coarse3_supported(hlen, p->lr[l - 1], p->lc[l - 1]);
         };
         // Two levels per WAVEFRONT (dwt2_fwd2_wave: A_l stays in registers, overlapping strips).  Correct and
         // tested, but NOT faster than two launches on MI355X (profiles/r02g_wbench_*.txt: 4096^2 31.3 us against
@@ -614,8 +625,9 @@ void build_schedule(pdwt_plan* p) {
                 if (const int K = p->chain_flags ? chain_at(l, dir != 0) : 0) { out.push_back({Step::CHAIN, l, K}); l += K - 1; continue; }
                 if (strip_at(l, dir != 0)) { out.push_back({Step::STRIP2, l, 2}); l++; }
                 else if (wave2_at(l, dir != 0)) { out.push_back({Step::WAVE2, l, 2}); l++; }
+                else if (coarse3_at(l, dir != 0)) { out.push_back({Step::PYR3, l, 3, 1}); l += 2; }
                 else if (pyr3_at(l, dir != 0)) { out.push_back({Step::PYR3, l, 3}); l += 2; }
-                else if ((pyr_at(l, dir != 0) && !strip_at(l + 1, dir != 0)) || (inv_pyr_l1 && dir == 1 && l == 1 && fusable && pair_ok(l))) { out.push_back({Step::PYR2, l, 2}); l++; }
+                else if ((pyr_at(l, dir != 0) && !strip_at(l + 1, dir != 0) && !coarse3_at(l + 1, dir != 0)) || (inv_pyr_l1 && dir == 1 && l == 1 && fusable && pair_ok(l))) { out.push_back({Step::PYR2, l, 2}); l++; }
                 else out.push_back({Step::LEVEL, l, 1});
             }
         }
@@ -1057,8 +1069,10 @@ int inverse_impl(pdwt_plan* p, int only = 0) {
             for (int k = 0; k < 9; k++) det[k] = p->band(3 * (l - 1) + 1 + k);
             Stamp st(p, "dwt2_inv_pyr3", &e);
             if (!run) continue;
-            e = launch_dwt2_inv_pyr3(approx_slot(p, l + 2), det, approx_slot(p, l - 1), p->lr[l - 1], p->lc[l - 1], hlen, p->rec, B,
-                                     p->stream);
+            e = s.coarse ? launch_dwt2_inv_coarse3(approx_slot(p, l + 2), det, approx_slot(p, l - 1), p->lr[l - 1], p->lc[l - 1], hlen, p->rec, B,
+                                                   p->stream)
+                         : launch_dwt2_inv_pyr3(approx_slot(p, l + 2), det, approx_slot(p, l - 1), p->lr[l - 1], p->lc[l - 1], hlen, p->rec, B,
+                                                p->stream);
         } else if (s.kind == Step::SWTF) {
             real_t* det[9] = {};
             for (int k = 0; k < 3 * s.K; k++) det[k] = p->band(3 * (l - 1) + 1 + k);
@@ -1503,6 +1517,7 @@ int pdwt_clone(pdwt_handle src, pdwt_handle* out) {
     int rc = build_layout(p);
     if (rc != PDWT_OK) { pdwt_destroy(p); return rc; }
     p->tune = src->tune;
+    p->inv_coarse3 = src->inv_coarse3;
     build_schedule(p);  // not copied: a chain step needs the clone's own hand-off flags
     e = hipStreamSynchronize(src->stream);
     if (e == hipSuccess)
@@ -2279,6 +2294,8 @@ int pdwt_set_tuning(const char* key, int value) {
     for (int k = 0; key && k < kKnobCount; ++k)
         if (!strcmp(key, names[k])) return set_knob((Knob)k, value);
     if (key && !strcmp(key, "chain_timeout")) return set_chain_timeout(value);  // not a dispatch knob, not part of the snapshot
+    // (tuning_knobs.inc says why this one is not a row; a plan keeps the value it was built with: pdwt_plan::inv_coarse3)
+    if (key && !strcmp(key, "inv_coarse3")) return set_inv_coarse3_mode(value);
     return fail(PDWT_ERR_ARG, "pdwt_set_tuning: unknown key %s", key ? key : "(null)");
 }
 

@@ -41,6 +41,7 @@ struct Step {
     int kind;
     int level;  // first (finest) level the launch works on
     int K;      // number of levels it covers
+    int coarse = 0;  // PYR3, inverse: the large-plane kernel (launch_dwt2_inv_coarse.hip) instead of the small-image pyramid
 };
 
 struct KernelStamp {
@@ -126,6 +127,7 @@ struct pdwt_plan {
 
     std::vector<pdwt::Step> sched_fwd, sched_inv;  // launch lists, in execution order
     pdwt::Tuning tune{};  // the dispatch knobs as they stood when the plan was created (launch.hpp: ActiveTuning)
+    int inv_coarse3 = 0;  // ... and the "inv_coarse3" key (launch.hpp: inv_coarse3_mode), which is not a row of the table
     // Step::CHAIN (several levels in one launch, dwt2_chain_kernels.hpp): per-tile hand-off flags of the forward and of the
     // inverse chain, batch x chain_tiles words each, zeroed once; every launch stamps them with a new epoch
     unsigned* chain_flags = nullptr;

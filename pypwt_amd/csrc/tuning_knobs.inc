@@ -37,3 +37,8 @@ PDWT_KNOB(wave2,         1, 1,  lab_env("PDWT_WAVE2") ? 1 : 0, "two forward leve
 PDWT_KNOB(swt_fused,     0, 2,  lab_env("PDWT_SWT_FUSED") ? atoi(lab_env("PDWT_SWT_FUSED")) : 1, "2-tap 2D SWT levels 1-3 / 4-6 and 4-tap pairs in one launch each (swt2_fused_kernels.hpp); 2: beyond the cache-size limit too")
 PDWT_KNOB(chain,         0, 3,  lab_env("PDWT_CHAIN") ? atoi(lab_env("PDWT_CHAIN")) : 0, "levels chained inside one launch: 0 never (opt-in: measured no faster, and the product stubs the kernels out), 1 one cache-resident image + batch inverses, 2 wherever supported (tests), 3 = 2 + batch forwards")
 PDWT_KNOB(reg1d,         0, 15, lab_env("PDWT_REG1D") ? (atoi(lab_env("PDWT_REG1D")) & 15) : 3, "1D levels three at a time in registers (dwt1_reg_kernels.hpp): bit 0 forward, bit 1 inverse, bits 2 / 3 lift the size limits")
+// ---- beside the table, like chain_timeout: "inv_coarse3" (0, 2; initially 1; PDWT_INV_COARSE3 in the measurement library) -- the inverse of
+// the three coarsest levels of a large plane in one launch (dwt2_inv_coarse_kernels.hpp): 0 never, 1 the size rule of build_schedule,
+// 2 wherever the kernel applies (tests).  The rows above are pinned one by one to the setters they replaced (tests/test_abi_cpu.py:
+// KNOB_RECORD, sixteen rows), so a key that never had such a setter lives in launch_dwt2_inv_coarse.hip (set_inv_coarse3_mode) and in
+// the plan (pdwt_plan::inv_coarse3: a clone rebuilds its launch lists from its source's value).
