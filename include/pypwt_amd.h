@@ -336,8 +336,8 @@ const char* pdwt_comm_last_error(void);
  *   - pointers from pdwt_volume_image_ptr / pdwt_volume_coeff_ptr are borrowed and valid while the volume lives.
  * pdwt_volume_layout is a pure host function (no device needed): the clamped level count into *nlevels, (depth, rows, cols) of
  * num 0 .. capacity - 1 into dims[3 num + {0,1,2}]; returns the number of bands 1 + 7 L, or a negative status.
- * Out of scope: 3D SWT through this constructor (pdwt_volume_create_swt below is the stationary transform), non-separable volumes, custom filter banks, cycle spinning, clone and add_wavelet, shrink / group /
- * proj_linf, the compiled Cython class, ShardedBatch / TiledWavelets for volumes, a fused kernel that does all three axes in
+ * Out of scope: 3D SWT through this constructor (pdwt_volume_create_swt below is the stationary transform), non-separable volumes, custom filter banks, cycle spinning, clone (add_wavelet, shrink, the group
+ * threshold and proj_linf are further down), the compiled Cython class, ShardedBatch / TiledWavelets for volumes, a fused kernel that does all three axes in
  * one read, a fused stats + threshold sweep. */
 typedef struct pdwt_volume* pdwt_volume_handle;
 int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char* wname, int levels, int mem_is_on_host,
@@ -426,6 +426,36 @@ int pdwt_volume_keep_largest_async(pdwt_volume_handle h, long long k, int do_thr
 int pdwt_volume_sparsify_slots(pdwt_volume_handle h, pdwt_real** d_threshold, unsigned long long** d_kept);
 int pdwt_volume_norms_async(pdwt_volume_handle h, double* d_out2);
 int pdwt_volume_read(pdwt_volume_handle h, void* dst, const void* d_src, long long bytes);
+
+/* The proximal operators and the linear combination of iterative reconstruction on a volume, decimated or stationary alike.
+ * A GROUP is, at level l and flat index i inside a sub-band, the seven detail sub-bands (aad[i] .. ddd[i]) -- and A_L[i] at the
+ * last level with do_thresh_appcoeffs, as the reference adds c_a at the last scale (common.cu:145-170).  The depth-low half of
+ * band A of a level below L (an intermediate) and padding are never a member and are never counted; nothing of these calls can be
+ * seen there by a later inverse, getter or operator.
+ *   - pdwt_volume_group_soft_threshold (wt.cu:329-336, common.cu:145-198, 311-341): every member becomes member * res with
+ *     res = 0 if ||g||_2 = 0, else max(1 - beta_l / ||g||_2, 0), in pdwt_real; beta_l = beta, divided by sqrt 2 once per level
+ *     under normalize, as for pdwt_volume_soft_threshold; the group of level L takes beta_L with or without A_L.  ONE launch;
+ *   - pdwt_volume_proj_linf (wt.cu:349-356, common.cu:101-137): copysign(min(|x|, beta), x) on every detail sub-band, and on A_L
+ *     with do_thresh_appcoeffs;  pdwt_volume_shrink (wt.cu:340-347, common.cu:347-371): x * (1 / (1 + beta)), the factor formed
+ *     once on the host in pdwt_real; same coverage.  The Python defaults are the reference's (pypwt.pyx:406);
+ *   - pdwt_volume_add_wavelet (wt.cu:622-655, common.cu:499-526): c += alpha * c_src on all 1 + 7 L sub-bands, one fused
+ *     multiply-add per value, on dst's stream, ordered after what is queued on src's stream.  Both handles must come from this
+ *     library (the same pdwt_real) and agree in shape, wavelet name, levels, transform kind and device: else PDWT_ERR_MISMATCH;
+ *   - pdwt_volume_group_norm (no reference counterpart; pdwt/TODO.txt:14 asks for it): *out = the sum over levels and positions of
+ *     ||g||_2, the l2,1 norm whose proximal map the group threshold is.  Every term in double (the members are converted, squared
+ *     and added in double, one double sqrt), the terms added in double in a fixed order without float atomics: two calls give the
+ *     same bits.  No normalize.  Reads only; blocks, like pdwt_volume_norms.  pdwt_volume_group_norm_async (no reference counterpart
+ *     either) leaves the result on the device and waits for nothing: in d_out[0], or in the volume's own slot when d_out is NULL; *d_slot, if given, receives the
+ *     address written.  The workspace is allocated by the first of the two that is called;
+ *   - PDWT_ERR_STATE after pdwt_volume_inverse, with nothing done: the four sweeps as the thresholds, the norm as
+ *     pdwt_volume_norms; PDWT_ERR_UNSUPPORTED before anything is launched for a size the index math cannot hold (a stationary
+ *     volume: sub-bands of 2^31 elements and more); PDWT_ERR_ARG: a null handle or a null out. */
+int pdwt_volume_group_soft_threshold(pdwt_volume_handle h, pdwt_real beta, int do_thresh_appcoeffs, int normalize);
+int pdwt_volume_proj_linf(pdwt_volume_handle h, pdwt_real beta, int do_thresh_appcoeffs);
+int pdwt_volume_shrink(pdwt_volume_handle h, pdwt_real beta, int do_thresh_appcoeffs);
+int pdwt_volume_add_wavelet(pdwt_volume_handle dst, pdwt_volume_handle src, pdwt_real alpha);
+int pdwt_volume_group_norm(pdwt_volume_handle h, int do_thresh_appcoeffs, double* out);
+int pdwt_volume_group_norm_async(pdwt_volume_handle h, int do_thresh_appcoeffs, double* d_out, double** d_slot);
 
 #ifdef __cplusplus
 }

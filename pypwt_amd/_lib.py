@@ -159,6 +159,12 @@ def signatures(real=C.c_float):
         "pdwt_volume_sparsify_slots": (C.c_int, [handle_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
         "pdwt_volume_norms_async": (C.c_int, [handle_t, C.c_void_p]),
         "pdwt_volume_read": (C.c_int, [handle_t, C.c_void_p, C.c_void_p, C.c_longlong]),
+        "pdwt_volume_group_soft_threshold": (C.c_int, [handle_t, real, C.c_int, C.c_int]),
+        "pdwt_volume_proj_linf": (C.c_int, [handle_t, real, C.c_int]),
+        "pdwt_volume_shrink": (C.c_int, [handle_t, real, C.c_int]),
+        "pdwt_volume_add_wavelet": (C.c_int, [handle_t, handle_t, real]),
+        "pdwt_volume_group_norm": (C.c_int, [handle_t, C.c_int, C.POINTER(C.c_double)]),
+        "pdwt_volume_group_norm_async": (C.c_int, [handle_t, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
         "pdwt_volume_set_filters": (C.c_int, [handle_t, C.c_int, realp, realp, realp, realp]),
         "pdwt_volume_set_depth_segments": (C.c_int, [handle_t, C.c_int, C.c_int, C.c_int]),
     }

@@ -248,6 +248,12 @@ hipError_t launch_vol_stats_reduce(const VolLevels& v, double* stats, hipStream_
 hipError_t launch_vol_norms(const double* stats, int nbands, double* out2, hipStream_t s);
 hipError_t launch_vol_table(const VolLevels& v, const double* stats, const double* sigma, int method, double visu, real_t* d_table, hipStream_t s);
 hipError_t launch_vol_expand(const VolLevels& v, const real_t* d_table, hipStream_t s);
+// the group operators of a volume, all levels in ONE launch: t gives every level's member pointers and pieces; with_app: A_L is the
+// eighth member at the last level.  The norm: one double per workgroup into partial[t.blk[t.nlevels]], their fixed-order sum into out[0]
+struct VolGroupTable;
+struct VolGroupBetas;
+hipError_t launch_vol_group_soft(const VolGroupTable& t, const VolGroupBetas& betas, int with_app, hipStream_t s);
+hipError_t launch_vol_group_norm(const VolGroupTable& t, int with_app, double* partial, double* out, hipStream_t s);
 hipError_t launch_circshift(const real_t* in, real_t* out, int batch, int Nr, int Nc, int sr, int sc, hipStream_t s);
 hipError_t launch_copy(const real_t* src, real_t* dst, long long n, hipStream_t s);  // 16-B grid-stride copy (n % 4 == 0)
 hipError_t launch_fill_hash(real_t* x, long long n, uint32_t seed, real_t scale, long long index_offset,

@@ -86,6 +86,9 @@ hipError_t launch_threshold_bands(int op, real_t* arena, const BandTable& t, con
     switch (op) {
         case EW_SOFT: hipLaunchKernelGGL((threshold_bands_kernel<EW_SOFT>), dim3(blocks), dim3(256), 0, s, arena, t, d_table); break;
         case EW_HARD: hipLaunchKernelGGL((threshold_bands_kernel<EW_HARD>), dim3(blocks), dim3(256), 0, s, arena, t, d_table); break;
+        // a volume's proj_linf and shrink (volume.cpp); the public per-band calls take soft and hard only
+        case EW_LINF: hipLaunchKernelGGL((threshold_bands_kernel<EW_LINF>), dim3(blocks), dim3(256), 0, s, arena, t, d_table); break;
+        case EW_SCALE: hipLaunchKernelGGL((threshold_bands_kernel<EW_SCALE>), dim3(blocks), dim3(256), 0, s, arena, t, d_table); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -53,4 +53,25 @@ hipError_t launch_vol_expand(const VolLevels& v, const real_t* d_table, hipStrea
     return hipGetLastError();
 }
 
+static int vol_group_blocks(const VolGroupTable& t) {
+    if (t.nlevels < 1 || t.nlevels > kVolMaxLevels || t.chunk < 4 || (t.chunk & 3)) return 0;
+    return t.blk[t.nlevels];
+}
+
+hipError_t launch_vol_group_soft(const VolGroupTable& t, const VolGroupBetas& betas, int with_app, hipStream_t s) {
+    const int blocks = vol_group_blocks(t);
+    if (blocks < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(vol_group_soft_kernel, dim3(blocks), dim3(kVolGroupThreads), 0, s, t, betas, with_app ? 1 : 0);
+    return hipGetLastError();
+}
+
+// partial: one double per workgroup (vol_group_partials of them); out: where the sum goes (device memory)
+hipError_t launch_vol_group_norm(const VolGroupTable& t, int with_app, double* partial, double* out, hipStream_t s) {
+    const int blocks = vol_group_blocks(t);
+    if (blocks < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(vol_group_norm_kernel, dim3(blocks), dim3(kVolGroupThreads), 0, s, t, with_app ? 1 : 0, partial);
+    hipLaunchKernelGGL(vol_group_norm_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, out);
+    return hipGetLastError();
+}
+
 }  // namespace pdwt

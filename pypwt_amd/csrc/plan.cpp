@@ -1474,6 +1474,22 @@ int pdwt::set_last_error(int code, const char* fmt, ...) {
     return code;
 }
 
+// the body of pdwt_threshold_bands, for every element-wise operator (plan.hpp)
+int pdwt::plan_sweep_bands(pdwt_plan* h, int op, const real_t* table, int table_on_device, const char* what) {
+    if (refuses(h, Entry::band_sweep))
+        return fail(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what);
+    PDWT_SETTLE_(h, Entry::band_sweep);
+    int rc = ensure_adaptive(h);
+    if (rc != PDWT_OK) return rc;
+    AdaptiveWs* w = h->adaptive;
+    if (!table_on_device) {
+        rc = stage_upload(h, w->table, table, (size_t)w->bt.nbands * w->bt.batch * sizeof(real_t), 0);
+        if (rc != PDWT_OK) return rc;
+        table = w->table;
+    }
+    return threshold_bands_impl(h, op, table);
+}
+
 // =============================================================================
 #pragma GCC visibility push(default)
 extern "C" {
@@ -1734,17 +1750,7 @@ int pdwt_threshold_bands(pdwt_handle h, int op, const real_t* table, int table_o
     CHECK_HANDLE(h);
     if (!table) return fail(PDWT_ERR_ARG, "threshold_bands: null table");
     if (op != EW_SOFT && op != EW_HARD) return fail(PDWT_ERR_ARG, "threshold_bands: op must be 0 (soft) or 1 (hard)");
-    PDWT_ENTER_OR(h, Entry::band_sweep,
-                  fail(PDWT_ERR_STATE, "threshold_bands: cannot threshold coefficients, as they were modified by inverse()"));
-    int rc = ensure_adaptive(h);
-    if (rc != PDWT_OK) return rc;
-    AdaptiveWs* w = h->adaptive;
-    if (!table_on_device) {
-        rc = stage_upload(h, w->table, table, (size_t)w->bt.nbands * w->bt.batch * sizeof(real_t), 0);
-        if (rc != PDWT_OK) return rc;
-        table = w->table;
-    }
-    return threshold_bands_impl(h, op, table);
+    return plan_sweep_bands(h, op, table, table_on_device, "threshold_bands");
 }
 
 int pdwt_denoise_async(pdwt_handle h, int method, int op, const double* sigma, int nsigma, int skip_zeros) {

@@ -87,6 +87,13 @@ int set_last_error(int code, const char* fmt, ...) __attribute__((format(printf,
 
 }  // namespace pdwt
 
+struct pdwt_plan;
+namespace pdwt {
+// pdwt_threshold_bands without its limit on `op`: any EwOp of launch.hpp per (band, image), NaN = leave alone (EW_SCALE: the entry
+// is the factor).  Internal: a volume's proj_linf / shrink reach the level plans through it; the public call takes soft and hard.
+int plan_sweep_bands(pdwt_plan* h, int op, const real_t* table, int table_on_device, const char* what);
+}  // namespace pdwt
+
 struct pdwt_plan {
     int device = 0;
     hipStream_t stream = nullptr;

@@ -12,6 +12,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <strings.h>
 
 #include <limits>
 
@@ -330,6 +331,33 @@ int select_magnitude_impl(VolumeDwt* v, long long k, int do_app, real_t* d_thres
     return PDWT_OK;
 }
 
+// The table of the group operators: per level the seven detail sub-bands in key order and, at the last level, A_L, as pointers
+// into the level's four band arrays (sub_ptr of the depth-low half is the array's start), and the pieces: about 2048 workgroups over
+// all levels, 2048 positions (14 K values) at least each.  No HIP call.
+void build_groups(pdwt_volume* v) {
+    VolGroupTable& t = v->groups;
+    t.nlevels = 0;
+    for (int l = 1; l <= v->nlevels; l++) {
+        real_t* band[4];
+        for (int b = 0; b < 4; b++) band[b] = v->sub_ptr(SubBand{l, 0, b, v->nz[l], v->nr[l], v->nc[l]});
+        vol_group_add_level(t, band, (long long)v->nz[l] * v->nr[l] * v->nc[l], l == v->nlevels);
+    }
+    vol_group_finish(t, 2048, 2048);
+}
+
+// the workspace of group_norm: the result slot and one partial sum per piece
+int ensure_group_ws(pdwt_volume* v) {
+    if (v->group_ws) return PDWT_OK;
+    const size_t bytes = align256((size_t)(1 + v->groups.blk[v->groups.nlevels]) * sizeof(double));
+    const hipError_t e = hipMalloc((void**)&v->group_ws, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        v->group_ws = nullptr;
+        return VFAIL(PDWT_ERR_NOMEM, "workspace of group_norm: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    }
+    return PDWT_OK;
+}
+
 // the one device block of a stationary volume, in bytes from its start (volume.hpp has the picture); no HIP call
 struct SwtLayout {
     size_t image = 0, stack = 0, bands = 0, band = 0, stats = 0, partial = 0, table = 0, total = 0;
@@ -370,6 +398,7 @@ namespace pdwt {
 VolumeDwt::~VolumeDwt() {
     if (!plans.empty()) (void)hipStreamSynchronize(stream);
     if (ops) free_ops(ops);
+    if (group_ws) (void)hipFree(group_ws);
     for (size_t i = plans.size(); i-- > 0;) pdwt_destroy(plans[i]);  // plans[0] may own the stream: last
     if (image) (void)hipFree(image);
 }
@@ -416,6 +445,7 @@ int VolumeDwt::inverse_levels() {
 
 // every plan's table is [band][image]: the level's threshold everywhere but on the depth-low half of band A
 int VolumeDwt::threshold(int op, const real_t* level_betas, real_t app_beta_or_nan, const char*) {
+    // (plan_sweep_bands: pdwt_threshold_bands for every element-wise operator -- proj_linf and shrink come this way too)
     PDWT_TRY(mark_current(this));
     std::vector<real_t> table;
     for (int l = 1; l <= nlevels; l++) {
@@ -423,7 +453,23 @@ int VolumeDwt::threshold(int op, const real_t* level_betas, real_t app_beta_or_n
         table.assign((size_t)4 * batch, level_betas[l - 1]);
         const real_t low_a = l == nlevels ? app_beta_or_nan : kLeave;  // A_L, or an intermediate
         for (int i = 0; i < half; i++) table[i] = low_a;
-        PDWT_TRY(pdwt_threshold_bands(plans[l - 1], op, table.data(), 0));
+        PDWT_TRY(plan_sweep_bands(plans[l - 1], op, table.data(), 0, "threshold_bands"));
+    }
+    return PDWT_OK;
+}
+
+int VolumeDwt::enter_sweep(const char*) { return mark_current(this); }
+
+// c += alpha c_other over every level's whole coefficient region (launch_axpy, as pdwt_add_wavelet): the padding stays zero, and
+// the intermediates A_1 .. A_{L-1} take part, which nothing can see -- the inverse overwrites A_{l-1} before it reads it, the
+// forward writes it, and no getter or operator reaches it
+int VolumeDwt::axpy(const pdwt_volume* other, real_t alpha) {
+    const VolumeDwt* src = static_cast<const VolumeDwt*>(other);
+    for (int l = 1; l <= nlevels; l++) {
+        const pdwt_plan* d = plans[l - 1];
+        const pdwt_plan* s = src->plans[l - 1];
+        if (d->coeff_elems != s->coeff_elems) return VFAIL(PDWT_ERR_MISMATCH, "add_wavelet: level %d is laid out differently", l);
+        HIP_TRY(launch_axpy(d->arena, s->arena, d->coeff_elems, alpha, stream));
     }
     return PDWT_OK;
 }
@@ -457,6 +503,7 @@ int VolumeDwt::set_filters(int n, const real_t* dec_lo, const real_t* dec_hi, co
 VolumeSwt::~VolumeSwt() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (block) (void)hipFree(block);
+    if (group_ws) (void)hipFree(group_ws);
     if (h_table) (void)hipHostFree(h_table);
     if (staged) (void)hipEventDestroy(staged);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
@@ -528,6 +575,16 @@ int VolumeSwt::ops_check(const char* what) const {
     return PDWT_OK;
 }
 
+int VolumeSwt::enter_sweep(const char* what) { return ops_check(what); }
+
+// the 4 L band arrays lie one behind the other, 256-B padded: one sweep (see VolumeDwt::axpy for the intermediates)
+int VolumeSwt::axpy(const pdwt_volume* other, real_t alpha) {
+    const VolumeSwt* src = static_cast<const VolumeSwt*>(other);
+    const long long per = band[1] - band[0];
+    HIP_TRY(launch_axpy(band[0], src->band[0], per * 4 * nlevels, alpha, stream));
+    return PDWT_OK;
+}
+
 int VolumeSwt::threshold(int op, const real_t* level_betas, real_t app_beta_or_nan, const char* what) {
     PDWT_TRY(ops_check(what));
     const int L = nlevels;
@@ -569,6 +626,26 @@ int threshold_entry(pdwt_volume_handle v, int op, real_t beta, int do_app, int n
     std::vector<real_t> level_betas;
     const real_t a = level_thresholds(beta, v->nlevels, do_app, normalize, &level_betas);
     return v->threshold(op, level_betas.data(), a, what);
+}
+
+// proj_linf / shrink: one value for every detail sub-band, and for A_L when asked for, through the sweep of the thresholds
+int uniform_entry(pdwt_volume_handle v, int op, real_t value, int do_app, const char* what) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->state == PDWT_INVERSE)
+        return VFAIL(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what);
+    DeviceGuard guard(v->device);
+    const std::vector<real_t> per((size_t)v->nlevels, value);
+    return v->threshold(op, per.data(), do_app ? value : kLeave, what);
+}
+
+int group_norm_entry(pdwt_volume_handle v, int do_app, double* d_out, double** d_slot) {
+    if (v->state == PDWT_INVERSE) return VFAIL(PDWT_ERR_STATE, "group_norm: the coefficients were modified by inverse()");
+    PDWT_TRY(v->enter_sweep("group_norm"));
+    PDWT_TRY(ensure_group_ws(v));
+    double* out = d_out ? d_out : v->group_ws;
+    HIP_TRY(launch_vol_group_norm(v->groups, do_app ? 1 : 0, v->group_ws + 1, out, v->stream));
+    if (d_slot) *d_slot = out;
+    return PDWT_OK;
 }
 
 // data into a sub-band or the image: nothing moves where the caller passes the destination itself
@@ -625,6 +702,7 @@ int pdwt_volume_create(const pdwt_real* img, int Nz, int Nr, int Nc, const char*
     }
     v->stream = (hipStream_t)stream;
     build_ranges(v);
+    build_groups(v);
     const size_t bytes = (size_t)Nz * Nr * Nc * sizeof(real_t);
     hipError_t e = hipMalloc((void**)&v->image, bytes);
     if (e != hipSuccess) {
@@ -690,6 +768,7 @@ int pdwt_volume_create_swt(const pdwt_real* img, int Nz, int Nr, int Nc, const c
     v->partial = reinterpret_cast<double*>(base + y.partial);
     v->table = reinterpret_cast<real_t*>(base + y.table);
     v->pieces = y.pieces;
+    build_groups(v);
     const long long n = (long long)Nz * Nr * Nc;
     for (int l = 1; l <= L; l++) {
         BandTable t{};
@@ -846,6 +925,70 @@ int pdwt_volume_soft_threshold(pdwt_volume_handle v, pdwt_real beta, int do_thre
 
 int pdwt_volume_hard_threshold(pdwt_volume_handle v, pdwt_real beta, int do_thresh_appcoeffs, int normalize) {
     return threshold_entry(v, EW_HARD, beta, do_thresh_appcoeffs, normalize, "hard_threshold");
+}
+
+int pdwt_volume_group_soft_threshold(pdwt_volume_handle v, pdwt_real beta, int do_thresh_appcoeffs, int normalize) {
+    const char* what = "group_soft_threshold";
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (v->state == PDWT_INVERSE)
+        return VFAIL(PDWT_ERR_STATE, "%s: cannot threshold coefficients, as they were modified by inverse()", what);
+    DeviceGuard guard(v->device);
+    PDWT_TRY(v->enter_sweep(what));
+    // the group of level L takes beta_L with or without A_L: the approximation has no threshold of its own here
+    std::vector<real_t> level_betas;
+    (void)level_thresholds(beta, v->nlevels, 0, normalize, &level_betas);
+    VolGroupBetas b{};
+    for (int l = 0; l < v->nlevels; l++) b.b[l] = level_betas[l];
+    HIP_TRY(launch_vol_group_soft(v->groups, b, do_thresh_appcoeffs ? 1 : 0, v->stream));
+    return PDWT_OK;
+}
+
+int pdwt_volume_proj_linf(pdwt_volume_handle v, pdwt_real beta, int do_thresh_appcoeffs) {
+    return uniform_entry(v, EW_LINF, beta, do_thresh_appcoeffs, "proj_linf");
+}
+
+int pdwt_volume_shrink(pdwt_volume_handle v, pdwt_real beta, int do_thresh_appcoeffs) {
+    const real_t factor = 1.0f / (1.0f + beta);  // formed once, in real_t (pdwt_shrink, plan.cpp)
+    return uniform_entry(v, EW_SCALE, factor, do_thresh_appcoeffs, "shrink");
+}
+
+int pdwt_volume_add_wavelet(pdwt_volume_handle dst, pdwt_volume_handle src, pdwt_real alpha) {
+    if (!dst || !src) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (dst->nlevels != src->nlevels || strcasecmp(dst->wname, src->wname))
+        return VFAIL(PDWT_ERR_MISMATCH, "add_wavelet(): right operand is not the same transform (wname, level)");
+    if (dst->Nz != src->Nz || dst->Nr != src->Nr || dst->Nc != src->Nc)
+        return VFAIL(PDWT_ERR_MISMATCH, "add_wavelet(): operands do not have the same geometry");
+    if (dst->do_swt != src->do_swt) return VFAIL(PDWT_ERR_MISMATCH, "add_wavelet(): operands should both use SWT or DWT");
+    if (dst->device != src->device) return VFAIL(PDWT_ERR_MISMATCH, "add_wavelet(): operands live on different devices");
+    if (dst->state == PDWT_INVERSE || src->state == PDWT_INVERSE)
+        return VFAIL(PDWT_ERR_STATE, "add_wavelet(): this operation makes no sense when wavelet has just been inverted");
+    DeviceGuard guard(dst->device);
+    PDWT_TRY(dst->enter_sweep("add_wavelet"));
+    if (src != dst) PDWT_TRY(src->enter_sweep("add_wavelet"));
+    if (src->stream != dst->stream) {  // after what is queued on the source's stream, without stopping the host
+        hipEvent_t done = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(done, src->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, done, 0);
+        (void)hipEventDestroy(done);  // (released once it has completed)
+        HIP_TRY(e);
+    }
+    return dst->axpy(src, alpha);
+}
+
+int pdwt_volume_group_norm_async(pdwt_volume_handle v, int do_thresh_appcoeffs, double* d_out, double** d_slot) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    DeviceGuard guard(v->device);
+    return group_norm_entry(v, do_thresh_appcoeffs, d_out, d_slot);
+}
+
+int pdwt_volume_group_norm(pdwt_volume_handle v, int do_thresh_appcoeffs, double* out) {
+    if (!v || !out) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_group_norm: null argument");
+    DeviceGuard guard(v->device);
+    PDWT_TRY(group_norm_entry(v, do_thresh_appcoeffs, nullptr, nullptr));
+    HIP_TRY(hipMemcpyAsync(out, v->group_ws, sizeof(double), hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    return PDWT_OK;
 }
 
 int pdwt_volume_norms(pdwt_volume_handle v, double out[2]) {

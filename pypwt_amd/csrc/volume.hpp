@@ -60,6 +60,10 @@ struct pdwt_volume {
     std::vector<int> seg_fwd_chosen, seg_inv_chosen;  // [l - 1]: the chooser's values (pdwt_volume_set_depth_segments restores them)
     std::vector<int> width;             // [l - 1]: columns per thread of level l's depth passes (a stationary volume: of the analysis)
     pdwt::FilterBank dec{}, rec{};
+    // the group operators (group_soft_threshold, group_norm): every level's members and pieces, fixed with the layout, and the
+    // norm's workspace -- [0] the result slot, then one partial sum per piece --, allocated by the first call that needs it
+    pdwt::VolGroupTable groups{};
+    double* group_ws = nullptr;
 
     explicit pdwt_volume(int swt) : do_swt(swt) {}
     pdwt_volume(const pdwt_volume&) = delete;
@@ -76,6 +80,11 @@ struct pdwt_volume {
     // the global soft / hard threshold: level_betas[l - 1] on the details of level l, app_beta_or_nan on A_L (NaN: left alone)
     virtual int threshold(int op, const real_t* level_betas, real_t app_beta_or_nan, const char* what) = 0;
     virtual int norms(double out[2]) = 0;
+    // what a sweep that writes the coefficients in place does first: the level plans of a decimated volume are told that their
+    // coefficients are current, a stationary volume checks the sweeps' size limit
+    virtual int enter_sweep(const char* what) = 0;
+    // add_wavelet: c += alpha c_other on this volume's stream; `other` is the same kind of object with the same layout
+    virtual int axpy(const pdwt_volume* other, real_t alpha) = 0;
     virtual int walk_steps(int level, bool inverse) const = 0;  // steps of a whole depth walk of that level
     // pdwt_volume_set_filters: the bank of every stage, or none of them where one refuses
     virtual int set_filters(int hlen, const real_t* dec_lo, const real_t* dec_hi, const real_t* rec_lo, const real_t* rec_hi);
@@ -112,6 +121,8 @@ struct VolumeDwt final : pdwt_volume {
     int copy(void* dst, const void* src, long long count, int kind) override;
     int threshold(int op, const real_t* level_betas, real_t app_beta_or_nan, const char* what) override;
     int norms(double out[2]) override;
+    int enter_sweep(const char* what) override;
+    int axpy(const pdwt_volume* other, real_t alpha) override;
     int walk_steps(int level, bool inverse) const override;
     int set_filters(int hlen, const real_t* dec_lo, const real_t* dec_hi, const real_t* rec_lo, const real_t* rec_hi) override;
     real_t* stack_ptr(int level) const;  // what level l's depth pass writes: its plan's image slot
@@ -151,6 +162,8 @@ struct VolumeSwt final : pdwt_volume {
     int copy(void* dst, const void* src, long long count, int kind) override;
     int threshold(int op, const real_t* level_betas, real_t app_beta_or_nan, const char* what) override;
     int norms(double out[2]) override;
+    int enter_sweep(const char* what) override;
+    int axpy(const pdwt_volume* other, real_t alpha) override;
     int walk_steps(int level, bool inverse) const override;
     Swt2DArgs level_args(int level, bool inverse) const;
     int ops_check(const char* what) const;  // the sweeps' limit of 2^31 - 1 values per sub-band

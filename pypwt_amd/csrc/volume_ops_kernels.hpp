@@ -11,7 +11,10 @@
 //   vol_norms_kernel         the sub-bands' sums added up, one wavefront, fixed order;
 //   vol_table_kernel         BayesShrink / VisuShrink thresholds per sub-band, one thread each;
 //   vol_expand_kernel        a table per sub-band written into every level plan's [4][2 div2(Nz)] table, one thread per entry,
-//                            NaN (leave alone) for the intermediate halves.
+//                            NaN (leave alone) for the intermediate halves;
+//   vol_group_soft_kernel    the group soft threshold over the seven sub-bands of a position (and A_L), all levels in one launch,
+//                            for the decimated and the stationary layout alike (VolGroupTable, further down);
+//   vol_group_norm_kernel    the l2,1 norm of the same groups: one partial sum per workgroup, vol_group_norm_final_kernel adds them.
 //
 // A range is (arena base of its level's plan, first, end) in elements from that base: the sweeps align their 16-B (fp64: 32-B)
 // groups by INDEX (ops_kernels.hpp: sweep_range), which is address alignment only because the base is the 256-B aligned arena;
@@ -158,6 +161,140 @@ PDWT_DEVICE double vol_threshold(int method, double sumsq, long long n, double s
     return var / sqrt(d > eps ? d : eps);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The GROUP operators (group_soft_threshold, group_norm): the group at position i of level l is the seven detail sub-bands
+// aad .. ddd at flat index i -- and A_L at the last level when asked for.  They live in the level's four band arrays [2 halves][n]:
+// a depth-low member at band + i, a depth-high one at band + n + i.
+//
+// Alignment: the arrays start 256-B aligned, so a group of four positions at i is a 16-B (fp64: 32-B) access for the low members
+// iff i % 4 == 0 and for the high ones iff (n + i) % 4 == 0.  Both hold together only when n % 4 == 0: such a level moves in whole
+// groups of four (pieces start at multiples of 4); a level with n % 4 != 0 goes value by value, one position per lane -- 4-B
+// (8-B) accesses that are still contiguous across the wavefront.
+
+constexpr int kVolGroupThreads = 256;
+constexpr int kVolGroupMembers = 8;  // the seven keys in `num` order, then A
+
+// Passed by value in the kernel-argument segment; built once with the layout.  Level l (index l - 1): m[k] = sub-band key k,
+// m[7] = A_L at the last level and null below it (an intermediate is no member); n = positions; its pieces of `chunk` positions
+// are the workgroups blk[l - 1] .. blk[l] - 1.
+struct VolGroupTable {
+    int nlevels;
+    long long chunk;
+    real_t* m[kVolMaxLevels][kVolGroupMembers];
+    long long n[kVolMaxLevels];
+    int blk[kVolMaxLevels + 1];
+};
+
+// the threshold of every level's groups (volume.cpp: level_thresholds)
+struct VolGroupBetas {
+    real_t b[kVolMaxLevels];
+};
+
+// Appends a level to `t` (level 1 first, on a table whose nlevels is 0; then vol_group_finish): band[b] = the start of band
+// array b (0 A, 1 H, 2 V, 3 D) of the level -- pdwt_coeff_ptr(plan, b) of a decimated volume, VolumeSwt::band[4 (l - 1) + b] of
+// a stationary one --, n = the values of one sub-band (one depth half).
+inline void vol_group_add_level(VolGroupTable& t, real_t* const band[4], long long n, bool last) {
+    const int l = t.nlevels++;
+    for (int k = 0; k < 7; k++) {
+        int half, b;
+        vol_key_place(k, &half, &b);
+        t.m[l][k] = band[b] + (long long)half * n;
+    }
+    t.m[l][7] = last ? band[0] : nullptr;
+    t.n[l] = n;
+}
+// The workgroup numbering: pieces of `chunk` positions, a multiple of 1024, at least `min_chunk` and about `target` of them over
+// all levels.  Returns the number of positions.
+inline long long vol_group_finish(VolGroupTable& t, long long target, long long min_chunk) {
+    long long total = 0;
+    for (int l = 0; l < t.nlevels; l++) total += t.n[l];
+    long long chunk = ((total + target - 1) / target + 1023) / 1024 * 1024;
+    if (chunk < min_chunk) chunk = min_chunk;
+    t.chunk = chunk;
+    long long blocks = 0;
+    for (int l = 0; l < t.nlevels; l++) {
+        t.blk[l] = (int)blocks;
+        blocks += (t.n[l] + chunk - 1) / chunk;  // at most target + nlevels in all
+    }
+    t.blk[t.nlevels] = (int)blocks;
+    return total;
+}
+
+// workgroup `blk`: its level (index l - 1) and its piece [*a, *e) of positions
+PDWT_DEVICE int vol_group_piece(const VolGroupTable& t, int blk, long long* a, long long* e) {
+    int l = 0;
+    while (l + 1 < t.nlevels && blk >= t.blk[l + 1]) l++;
+    const long long lo = (long long)(blk - t.blk[l]) * t.chunk;
+    *a = lo;
+    *e = lo + t.chunk < t.n[l] ? lo + t.chunk : t.n[l];
+    return l;
+}
+
+// head / groups / tail of piece [a, e) of a level of n positions: [*g0, *g1) moves in groups of four, every member on an aligned
+// address; [a, *g0) and [*g1, e) go value by value
+PDWT_DEVICE void vol_group_split(long long n, long long a, long long e, long long* g0, long long* g1) {
+    if (n & 3) {  // the two depth halves have different phases: no group
+        *g0 = *g1 = e;
+        return;
+    }
+    long long a4 = (a + 3) & ~3LL, e4 = e & ~3LL;
+    if (a4 > e) a4 = e;
+    if (e4 < a4) e4 = a4;
+    *g0 = a4;
+    *g1 = e4;
+}
+
+// thread `tid` of `nthreads` over its piece: one(i) for a single position, four(i) for the group i .. i + 3
+template <typename FS, typename FV>
+PDWT_DEVICE void vol_group_sweep(long long n, long long a, long long e, int tid, int nthreads, FS one, FV four) {
+    long long g0, g1;
+    vol_group_split(n, a, e, &g0, &g1);
+    for (long long i = a + tid; i < g0; i += nthreads) one(i);
+    for (long long i = g0 + 4LL * tid; i < g1; i += 4LL * nthreads) four(i);
+    for (long long i = g1 + tid; i < e; i += nthreads) one(i);
+}
+
+// The sum of squares of a group, member by member, and the factor max(1 - beta / ||g||_2, 0) out of it, in real_t.
+//   fp32: the plain sum and the plain formula of group_soft_kernel (ops_kernels.hpp).
+//   fp64: the same value by a better conditioned route.  1 - beta / ||g|| cancels where a group is just above its threshold, and
+//         a member far larger than what is left of it multiplies the half ulp of beta / ||g|| into the result: on the MI355X
+//         the plain formula missed 8 * 2^-52 max(|band|, 1) by a sixth (tests/test_gpu_volume_prox.py, 8 x 8 x 8 stationary,
+//         where the survivors of level 1 keep only a small part of their length).  So every product and addition of the sum keeps its rounding
+//         error (an fma for the product, Knuth's two-sum for the addition), the square root gets its own error back from the
+//         exact remainder, and the factor is (||g|| - beta) / ||g||, whose subtraction is then exact to the last bit: the result
+//         is good to about two ulps of ITSELF.  The kernel is bound by memory: the extra flops are free.
+struct VolSumSq {
+    real_t hi, lo;
+};
+PDWT_DEVICE void vol_sumsq_add(VolSumSq& s, real_t x) {
+#ifdef PDWT_DOUBLE
+#pragma clang fp contract(off)  // (the error terms are exact only if no product is fused into a neighbouring sum)
+    const double p = x * x, e = fma(x, x, -p);
+    const double t = s.hi + p, bb = t - s.hi;
+    const double err = (s.hi - (t - bb)) + (p - bb);
+    s.hi = t;
+    s.lo += e + err;
+#else
+    s.hi += x * x;
+#endif
+}
+PDWT_DEVICE real_t vol_group_res(const VolSumSq& s, real_t beta) {
+#ifdef PDWT_DOUBLE
+#pragma clang fp contract(off)
+    if (s.hi - s.hi == 0.0) {  // (an overflowed or NaN sum takes the plain formula below)
+        const double nrm = sqrt(s.hi + s.lo);
+        if (nrm == 0.0) return 0.0;
+        const double rest = fma(-nrm, nrm, s.hi) + s.lo;  // sum - nrm^2
+        const double d = (nrm - beta) + rest / (2.0 * nrm);
+        return fmax(d / nrm, 0.0);
+    }
+#endif
+    const real_t nrm = sqrt(s.hi);
+    return nrm == real_t(0) ? real_t(0) : fmax(real_t(1) - beta / nrm, real_t(0));
+}
+// a member's share of a group_norm term: its square in double
+PDWT_DEVICE double vol_group_sq(real_t x) { return (double)x * (double)x; }
+
 #if !defined(PDWT_CPU_EMU) && !defined(PDWT_INLINE_HELPERS_ONLY)  // (ops_kernels.hpp; volume.cpp takes the tables only)
 
 // The histogram pass of the rank select over the pieces of `t`: grid = the pieces (t.blk[nranges], or t.blk[nranges - 1] without
@@ -286,6 +423,131 @@ __global__ void __launch_bounds__(256) vol_expand_kernel(VolLevels v, const real
     const int num = vol_num_of(level, v.nlevels, band, img, hz);
     v.table[level - 1][at] = num < 0 ? (real_t)__builtin_nan("") : table[num];
 }
+
+// The seven members of a level (and A when `has_a`) at constant indices, so that nothing is indexed at run time and nothing
+// lands in scratch.  F(k, pointer) for k = 0 .. 6, then 7.
+#define PDWT_VOL_GROUP_EACH(F) \
+    F(0, m0) F(1, m1) F(2, m2) F(3, m3) F(4, m4) F(5, m5) F(6, m6)
+
+// member <- member * max(1 - beta_l / ||g||_2, 0) for every group of every level in ONE launch: grid = t.blk[nlevels] pieces.
+__global__ void __launch_bounds__(kVolGroupThreads) vol_group_soft_kernel(VolGroupTable t, VolGroupBetas betas, int with_app) {
+    long long a, e;
+    const int l = vol_group_piece(t, blockIdx.x, &a, &e);
+    real_t* const m0 = t.m[l][0];
+    real_t* const m1 = t.m[l][1];
+    real_t* const m2 = t.m[l][2];
+    real_t* const m3 = t.m[l][3];
+    real_t* const m4 = t.m[l][4];
+    real_t* const m5 = t.m[l][5];
+    real_t* const m6 = t.m[l][6];
+    real_t* const ma = with_app ? t.m[l][7] : nullptr;
+    const real_t beta = betas.b[l];
+    vol_group_sweep(
+        t.n[l], a, e, threadIdx.x, kVolGroupThreads,
+        [&](long long i) {
+            VolSumSq ss = {real_t(0), real_t(0)};
+#define PDWT_VG_LOAD(k, p)   \
+    const real_t x##k = p[i]; \
+    vol_sumsq_add(ss, x##k);
+            PDWT_VOL_GROUP_EACH(PDWT_VG_LOAD)
+#undef PDWT_VG_LOAD
+            real_t xa = real_t(0);
+            if (ma) {
+                xa = ma[i];
+                vol_sumsq_add(ss, xa);
+            }
+            const real_t res = vol_group_res(ss, beta);
+#define PDWT_VG_STORE(k, p) p[i] = x##k * res;
+            PDWT_VOL_GROUP_EACH(PDWT_VG_STORE)
+#undef PDWT_VG_STORE
+            if (ma) ma[i] = xa * res;
+        },
+        [&](long long i) {
+            VolSumSq sx = {real_t(0), real_t(0)}, sy = sx, sz = sx, sw = sx;
+#define PDWT_VG_LOAD(k, p)                                   \
+    real4_t v##k = *reinterpret_cast<const real4_t*>(p + i); \
+    vol_sumsq_add(sx, v##k.x), vol_sumsq_add(sy, v##k.y), vol_sumsq_add(sz, v##k.z), vol_sumsq_add(sw, v##k.w);
+            PDWT_VOL_GROUP_EACH(PDWT_VG_LOAD)
+#undef PDWT_VG_LOAD
+            real4_t va = real4_t{real_t(0), real_t(0), real_t(0), real_t(0)};
+            if (ma) {
+                va = *reinterpret_cast<const real4_t*>(ma + i);
+                vol_sumsq_add(sx, va.x), vol_sumsq_add(sy, va.y), vol_sumsq_add(sz, va.z), vol_sumsq_add(sw, va.w);
+            }
+            const real_t rx = vol_group_res(sx, beta), ry = vol_group_res(sy, beta), rz = vol_group_res(sz, beta), rw = vol_group_res(sw, beta);
+#define PDWT_VG_STORE(k, p)                                       \
+    v##k.x *= rx, v##k.y *= ry, v##k.z *= rz, v##k.w *= rw;       \
+    *reinterpret_cast<real4_t*>(p + i) = v##k;
+            PDWT_VOL_GROUP_EACH(PDWT_VG_STORE)
+#undef PDWT_VG_STORE
+            if (ma) {
+                va.x *= rx, va.y *= ry, va.z *= rz, va.w *= rw;
+                *reinterpret_cast<real4_t*>(ma + i) = va;
+            }
+        });
+}
+
+// partial[blk] = the sum of ||g||_2 over the workgroup's piece: every term in double (the members' squares converted first, one
+// double sqrt), added in a fixed order -- a lane's own terms, wave shuffles, one LDS step.  Reads only.
+__global__ void __launch_bounds__(kVolGroupThreads) vol_group_norm_kernel(VolGroupTable t, int with_app, double* __restrict__ partial) {
+    long long a, e;
+    const int l = vol_group_piece(t, blockIdx.x, &a, &e);
+    const real_t* const m0 = t.m[l][0];
+    const real_t* const m1 = t.m[l][1];
+    const real_t* const m2 = t.m[l][2];
+    const real_t* const m3 = t.m[l][3];
+    const real_t* const m4 = t.m[l][4];
+    const real_t* const m5 = t.m[l][5];
+    const real_t* const m6 = t.m[l][6];
+    const real_t* const ma = with_app ? t.m[l][7] : nullptr;
+    double s = 0.0;
+    vol_group_sweep(
+        t.n[l], a, e, threadIdx.x, kVolGroupThreads,
+        [&](long long i) {
+            double ss = 0.0;
+#define PDWT_VG_LOAD(k, p) ss += vol_group_sq(p[i]);
+            PDWT_VOL_GROUP_EACH(PDWT_VG_LOAD)
+#undef PDWT_VG_LOAD
+            if (ma) ss += vol_group_sq(ma[i]);
+            s += sqrt(ss);
+        },
+        [&](long long i) {
+            double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
+#define PDWT_VG_LOAD(k, p)                                                   \
+    {                                                                        \
+        const real4_t v = *reinterpret_cast<const real4_t*>(p + i);          \
+        sx += vol_group_sq(v.x), sy += vol_group_sq(v.y), sz += vol_group_sq(v.z), sw += vol_group_sq(v.w); \
+    }
+            PDWT_VOL_GROUP_EACH(PDWT_VG_LOAD)
+#undef PDWT_VG_LOAD
+            if (ma) {
+                const real4_t v = *reinterpret_cast<const real4_t*>(ma + i);
+                sx += vol_group_sq(v.x), sy += vol_group_sq(v.y), sz += vol_group_sq(v.z), sw += vol_group_sq(v.w);
+            }
+            s += sqrt(sx);
+            s += sqrt(sy);
+            s += sqrt(sz);
+            s += sqrt(sw);
+        });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    __shared__ double part[kVolGroupThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// one wavefront: out[0] = the sum of the workgroups' partial sums, in a fixed order
+__global__ void __launch_bounds__(64) vol_group_norm_final_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ out) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 64) s += partial[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (threadIdx.x == 0) out[0] = s;
+}
+
+#undef PDWT_VOL_GROUP_EACH
 
 #endif  // !PDWT_CPU_EMU && !PDWT_INLINE_HELPERS_ONLY
 

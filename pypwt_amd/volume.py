@@ -9,6 +9,7 @@ rest of the library (pywt's "periodization").  ctypes binding only.
     W.forward(); W.denoise("BayesShrink"); W.inverse()        # the threshold of every sub-band from the data, on the device
     W.forward(); W.keep_largest(fraction=0.05); W.inverse()   # best K-term approximation
     W = Wavelets3D(vol, "db4", 3, do_swt=1); W.forward(); W.soft_threshold(10); W.inverse()   # translation-invariant denoising
+    W.group_soft_threshold(t); W.proj_linf(t); W.shrink(t); W.add_wavelet(W_old, -0.5); W.group_norm()   # the proximal steps
 """
 import ctypes as C
 
@@ -245,6 +246,42 @@ class Wavelets3D(object):
     def hard_threshold(self, beta, do_threshold_appcoeffs=0, normalize=0):
         """x 1_{|x| > t}"""
         self._threshold(self._lib.pdwt_volume_hard_threshold, beta, do_threshold_appcoeffs, normalize)
+
+    def group_soft_threshold(self, beta, do_threshold_appcoeffs=0, normalize=0):
+        """Group soft threshold: at every level and position the seven detail coefficients 'aad' .. 'ddd' (and A_L at the last
+        level with ``do_threshold_appcoeffs``) shrink together by max(1 - t / ||g||_2, 0); ``normalize`` as for ``soft_threshold``.
+        One launch over all levels, decimated and stationary volumes alike."""
+        self._threshold(self._lib.pdwt_volume_group_soft_threshold, beta, do_threshold_appcoeffs, normalize)
+
+    def proj_linf(self, beta, do_threshold_appcoeffs=1):
+        """Projection on the l-infinity ball of radius beta: sign(x) min(|x|, beta) on the details, and on A_L with the flag."""
+        self._refused(self._lib.pdwt_volume_proj_linf(self._h, float(beta), int(do_threshold_appcoeffs)))
+
+    def shrink(self, beta, do_threshold_appcoeffs=1):
+        """x / (1 + beta) on the details, and on A_L with the flag: the proximal map of beta/2 ||.||_2^2."""
+        self._refused(self._lib.pdwt_volume_shrink(self._h, float(beta), int(do_threshold_appcoeffs)))
+
+    def add_wavelet(self, W, alpha=1.0):
+        """c += alpha * c_W on every sub-band.  ``W`` must be a volume of the same class, shape, wavelet, levels, transform kind
+        and device (else it raises, with nothing done); the work runs on this volume's stream, after what is queued on ``W``'s."""
+        if not isinstance(W, Wavelets3D) or W._variant != self._variant:
+            raise ValueError("Wavelets3D.add_wavelet: the right operand must be a %s" % type(self).__name__)
+        self._refused(self._lib.pdwt_volume_add_wavelet(self._h, W._h, float(alpha)))
+
+    def group_norm(self, do_threshold_appcoeffs=0):
+        """The l2,1 norm ``group_soft_threshold`` is the proximal map of: the sum over levels and positions of the Euclidean norm of
+        the group, accumulated in float64 in a fixed order (two calls give the same bits).  Blocks."""
+        out = C.c_double(0.0)
+        self._check(self._lib.pdwt_volume_group_norm(self._h, int(do_threshold_appcoeffs), C.byref(out)), "group_norm")
+        return float(out.value)
+
+    def group_norm_device(self, out=None, do_threshold_appcoeffs=0):
+        """``group_norm`` as one float64 ON THE DEVICE, enqueued and not waited for: ``out`` if given (a device array of one
+        float64), else a (1,) view of the volume's own slot."""
+        arg, view = self._out(out, 1, "group_norm_device")
+        slot = C.c_void_p()
+        self._check(self._lib.pdwt_volume_group_norm_async(self._h, int(do_threshold_appcoeffs), arg, C.byref(slot)), "group_norm_device")
+        return view if view is not None else self._view(slot.value, (1,), np.float64)
 
     def norms(self):
         """(sum |c|, sum c^2) over all coefficients, accumulated in float64."""

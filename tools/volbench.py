@@ -31,6 +31,16 @@ the same 3 volumes of bytes).
     python tools/volbench.py --swt --summarize DIR --case N                                  depth pass per level against the copy
     (the three outputs together are profiles/volume_swt_bench.txt)
 
+--prox: the proximal operators (group_soft_threshold, group_norm, proj_linf, shrink, add_wavelet) on 256^3 and 512^3 db4 with three
+levels, decimated; on 512 x 511 x 511 (div2 rounds up: its sub-bands have 256^3, 128^3, 64^3 values, all multiples of 4) and on
+510^3 (255^3 values at level 1: the value-by-value path), decimated; and on 256^3 stationary.  Every line is timed twice by device
+events after a warm-up.  In the same run, as yardsticks: the global soft_threshold sweep of the same volume and a flat copy of
+the same number of values.  GB/s is the operator's ALGORITHMIC bytes over the faster time: the details read and written for the
+two thresholds (8 B per detail value), read for the norm (4 B), all sub-bands read and written for proj_linf / shrink with the
+approximation (8 B), two volumes read and one written for add_wavelet (12 B), 8 B per value for the copy.
+
+    python tools/volbench.py --prox                > profiles/volume_proxbench.txt
+
 --profile: a short run of ONE case with one level (so that every kernel name in the trace belongs to level 1) plus the copy and
 the 2D level of the same bytes, for rocprofv3; --summarize reads the kernel trace of such a run and reports, per depth kernel,
 its share of the copy next to the share the 2D level-1 kernel reaches.
@@ -225,6 +235,72 @@ def run_ops(args):
         W.cleanup()
 
 
+# (name, shape, wavelet, levels, stationary)
+PROX_CASES = [("256^3 db4", (256, 256, 256), "db4", 3, 0), ("512^3 db4", (512, 512, 512), "db4", 3, 0),
+              ("512x511x511 db4", (512, 511, 511), "db4", 3, 0), ("510^3 db4", (510, 510, 510), "db4", 3, 0),
+              ("256^3 db4 swt", (256, 256, 256), "db4", 3, 1)]
+
+
+def run_prox(args):
+    from pypwt_amd import BatchedWavelets
+    ev = Events()
+    print("# volbench --prox: proximal operators on the coefficients of a volume, fp32, %d calls per timing after %d warm-up calls; every line timed twice"
+          % (args.reps, args.warmup))
+    print("# GB/s: algorithmic bytes per call / the faster time (see the module docstring); 'of soft': the operator's rate over the soft_threshold sweep's")
+    print("# %-16s %-22s %10s %10s %10s %8s" % ("case", "operator", "ms (1st)", "ms (2nd)", "GB/s", "of soft"))
+    for k, (name, shape, wname, levels, swt) in enumerate(PROX_CASES):
+        if args.case is not None and k != args.case:
+            continue
+        W, W2 = make_volume(shape, wname, levels, swt), make_volume(shape, wname, levels, swt)
+        W.forward(), W2.forward()
+        lib, h = W._lib, W._h
+        sizes = [int(np.prod(W.band_shape(num))) for num in range(W.nbands)]
+        n_all, n_det = sum(sizes), sum(sizes[1:])
+        n_l = [sizes[1 + 7 * l] for l in range(W.levels)]
+
+        def ok(rc):
+            assert rc == 0, rc
+
+        def soft():
+            ok(lib.pdwt_volume_soft_threshold(h, 10.0, 0, 0))
+
+        def group():
+            ok(lib.pdwt_volume_group_soft_threshold(h, 10.0, 0, 0))
+
+        def norm():
+            ok(lib.pdwt_volume_group_norm_async(h, 0, None, None))
+
+        def linf():
+            ok(lib.pdwt_volume_proj_linf(h, 10.0, 1))
+
+        def shrink():
+            ok(lib.pdwt_volume_shrink(h, 0.001, 1))
+
+        def axpy():
+            ok(lib.pdwt_volume_add_wavelet(h, W2._h, 0.001))
+
+        rows = [("soft_threshold", soft, 8 * n_det), ("group_soft_threshold", group, 8 * n_det), ("group_norm", norm, 4 * n_det),
+                ("proj_linf", linf, 8 * n_all), ("shrink", shrink, 8 * n_all), ("add_wavelet", axpy, 12 * n_all)]
+        rate = {}
+        for oname, fn, nbytes in rows:
+            ok(lib.pdwt_volume_forward(h))  # dense coefficients under every operator
+            t = [ev.time(W._stream(), fn, args.reps, args.warmup) for _ in range(2)]
+            rate[oname] = nbytes / (min(t) * 1e6)
+            print("  %-16s %-22s %10.4f %10.4f %10.0f %8.2f" % (name, oname, t[0], t[1], rate[oname], rate[oname] / rate["soft_threshold"]))
+        W.cleanup(), W2.cleanup()
+        B = BatchedWavelets(n_all // (shape[1] * shape[2]) + 1, shape[1], shape[2], "haar", 1)
+        B.fill_hash(3)
+        elems = min(n_all, B.copy_capacity())
+        t = [B.time_copy(elems, args.reps) / 1e3 for _ in range(2)]
+        B.cleanup()
+        print("  %-16s %-22s %10.4f %10.4f %10.0f %8.2f" % (name, "flat copy, %d values" % elems, t[0], t[1], 8 * elems / (min(t) * 1e6),
+                                                            8 * elems / (min(t) * 1e6) / rate["soft_threshold"]))
+        print("  %-16s positions per level %s (%s); group_soft_threshold reaches %.2f of the soft_threshold sweep"
+              % (name, n_l, ", ".join("groups of four" if n % 4 == 0 else "value by value" for n in n_l),
+                 rate["group_soft_threshold"] / rate["soft_threshold"]))
+        sys.stdout.flush()
+
+
 SWT_CASES = [("256^3 db4", (256, 256, 256), "db4", 3), ("256^3 haar", (256, 256, 256), "haar", 3)]
 
 
@@ -357,6 +433,7 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--ops", action="store_true")
     ap.add_argument("--swt", action="store_true")
+    ap.add_argument("--prox", action="store_true")
     ap.add_argument("--summarize", default=None)
     ap.add_argument("--list", action="store_true")
     args = ap.parse_args()
@@ -364,7 +441,9 @@ def main():
         for k, c in enumerate(CASES):
             print(k, c, "bytes/sample per direction %.1f" % bytes_per_sample(c[1], c[3]))
         return
-    if args.swt:
+    if args.prox:
+        run_prox(args)
+    elif args.swt:
         if args.summarize:
             run_swt_summarize(args)
         elif args.profile:
