@@ -119,7 +119,7 @@ int pdwt_set_tuning(const char* key, int value);
  * 0: never; 1 (default): where that launch writes more than 2^20 and at most 2^22 samples over the batch (the 2048^2 plane of
  * one 4096^2 image); 2: wherever the kernel applies (tests).  Read when a plan is created, like the others. */
 
-/* Test hooks of a volume (tests/test_gpu_volume_taps.py).  Custom filter banks on volumes are NOT part of the product: these two
+/* Test hooks of a volume (tests/test_gpu_volume_taps.py).  Custom filter banks on volumes are NOT part of the product: these
  * exist so that every depth-kernel instantiation can be run with a bank whose every tap counts, at every segment length.
  *
  * The first replaces the four filters of the volume's depth passes and of every level's 2D plan (the plans' own
@@ -133,6 +133,11 @@ int pdwt_volume_set_filters(pdwt_volume_handle h, int hlen, const pdwt_real* dec
  * forward, the synthesis' step count inverse --, else PDWT_ERR_ARG and nothing is changed.  pdwt_volume_depth_schedule reports
  * what is in force. */
 int pdwt_volume_set_depth_segments(pdwt_volume_handle h, int level, int seg_fwd, int seg_inv);
+/* The columns per thread of the depth pass of level `level` (1 .. nlevels): of the analysis (inverse = 0) or of the synthesis
+ * (inverse != 0).  pdwt_volume_depth_schedule reports the analysis' only; a stationary volume's synthesis holds twice the window and
+ * may take fewer columns (tests/test_gpu_volume_swt_taps.py asserts which instantiation ran), a decimated volume has one width for
+ * both directions.  Returns the width (1, 2 or 4), or PDWT_ERR_ARG for a null handle or a level out of range. */
+int pdwt_volume_depth_width(pdwt_volume_handle h, int level, int inverse);
 
 #ifdef __cplusplus
 }

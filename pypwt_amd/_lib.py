@@ -167,6 +167,7 @@ def signatures(real=C.c_float):
         "pdwt_volume_group_norm_async": (C.c_int, [handle_t, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
         "pdwt_volume_set_filters": (C.c_int, [handle_t, C.c_int, realp, realp, realp, realp]),
         "pdwt_volume_set_depth_segments": (C.c_int, [handle_t, C.c_int, C.c_int, C.c_int]),
+        "pdwt_volume_depth_width": (C.c_int, [handle_t, C.c_int, C.c_int]),
     }
 
 

@@ -1161,5 +1161,11 @@ int pdwt_volume_set_depth_segments(pdwt_volume_handle v, int level, int seg_fwd,
     return PDWT_OK;
 }
 
+int pdwt_volume_depth_width(pdwt_volume_handle v, int level, int inverse) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (level < 1 || level > v->nlevels) return VFAIL(PDWT_ERR_ARG, "level %d out of range (1 .. %d)", level, v->nlevels);
+    return v->depth_width(level, inverse != 0);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -86,6 +86,8 @@ struct pdwt_volume {
     // add_wavelet: c += alpha c_other on this volume's stream; `other` is the same kind of object with the same layout
     virtual int axpy(const pdwt_volume* other, real_t alpha) = 0;
     virtual int walk_steps(int level, bool inverse) const = 0;  // steps of a whole depth walk of that level
+    // columns per thread of level l's depth pass in that direction (pdwt_volume_depth_width)
+    virtual int depth_width(int level, bool /*inverse*/) const { return width[level - 1]; }
     // pdwt_volume_set_filters: the bank of every stage, or none of them where one refuses
     virtual int set_filters(int hlen, const real_t* dec_lo, const real_t* dec_hi, const real_t* rec_lo, const real_t* rec_hi);
 };
@@ -165,6 +167,7 @@ struct VolumeSwt final : pdwt_volume {
     int enter_sweep(const char* what) override;
     int axpy(const pdwt_volume* other, real_t alpha) override;
     int walk_steps(int level, bool inverse) const override;
+    int depth_width(int level, bool inverse) const override { return (inverse ? width_inv : width)[level - 1]; }
     Swt2DArgs level_args(int level, bool inverse) const;
     int ops_check(const char* what) const;  // the sweeps' limit of 2^31 - 1 values per sub-band
 };

@@ -168,6 +168,10 @@ class Wavelets3D(object):
         chooser's value."""
         self._check(self._lib.pdwt_volume_set_depth_segments(self._h, int(level), int(seg_fwd), int(seg_inv)), "_set_depth_segments")
 
+    def _depth_width(self, level, inverse):
+        """Test plumbing (pdwt_volume_depth_width): columns per thread of the depth analysis (inverse false) or synthesis of `level`."""
+        return self._check(self._lib.pdwt_volume_depth_width(self._h, int(level), 1 if inverse else 0), "_depth_width")
+
     def band_shape(self, num):
         return self._shapes[num]
 

@@ -12,15 +12,18 @@ one fp32 ulp of the band's maximum.
 
 K = 4.  The largest err / noise measured on the MI355X is 2.50 (the inverse strip kernels; every family and direction:
 profiles/taps_parity.txt); through the depth kernels of a volume it is 2.00 (every even length 4-40, both widths, both directions, forced
-depth segments: profiles/volume_taps_parity.txt).  So 4 holds.  (K may be raised to twice the largest ratio a correct kernel needs, never beyond 16;
-tests/test_tap_banks_cpu.py and tests/test_volume_taps_cpu.py demand that zeroing any single tap still moves the oracle by 1000 x the
+depth segments: profiles/volume_taps_parity.txt), through the a-trous depth kernels of a stationary volume 1.75 (every even length 2-40,
+every width of both directions, dilations 1-4: profiles/volume_swt_taps_parity.txt).  So 4 holds.  (K may be raised to twice the largest ratio a correct kernel needs, never beyond 16;
+tests/test_tap_banks_cpu.py, tests/test_volume_taps_cpu.py and tests/test_volume_swt_taps_cpu.py demand that zeroing any single tap still moves the oracle by 1000 x the
 tolerance, whatever K is.)
 
-The volume_* helpers below are the same rule for one level of a volume: the composition of tests/volume_ref.py in the place of the oracle."""
+The volume_* helpers below are the same rule for one level of a volume: the composition of tests/volume_ref.py in the place of the oracle;
+the volume_swt_* helpers for any number of levels of a stationary volume: the per-axis composition of tests/volume_swt_ref.py."""
 import numpy as np
 
 from oracle import oracle
 import volume_ref
+import volume_swt_ref
 
 K = 4.0
 K_MAX = 16.0
@@ -125,3 +128,47 @@ def depth_tap_factor(x, filt, which, j, ref, tols):
     tolerances in the band it moves most; ref, tols: volume_forward_reference(x, filt)."""
     got = volume_ref.forward(x, None, 1, True, filt=filt, depth_filt=without_tap(filt, which, j))
     return max(float(np.abs(g.astype(np.float64) - r).max()) / tol for g, r, (tol, _) in zip(got, ref, tols))
+
+
+# ---- stationary volumes: `levels` levels of Wavelets3D(..., do_swt=1) (tests/test_volume_swt_taps_cpu.py, tests/test_gpu_volume_swt_taps.py)
+
+# (taps, shape, levels): the smallest volumes that reach a dilation above 1 -- the level clamp wants min(shape) >= 2^L (n - 1)
+SWT_DILATED = ((4, (25, 24, 28), 3),    # dilation 4; odd depth: one orbit at every level
+               (10, (37, 36, 40), 2),   # the inverse on half the forward's columns
+               (18, (69, 68, 72), 2),   # taps staged in LDS; the inverse on one column
+               (4, (24, 25, 27), 3))    # depth 24: 2 and 4 orbits at dilations 2 and 4; planes of 675 samples, one column per lane
+
+
+def swt_dilated_input(index):
+    """(bank, volume) of SWT_DILATED[index]."""
+    n, shape, _ = SWT_DILATED[index]
+    return bank(n, 2000 + n), volume_input(shape, 4300 + index)
+
+
+def volume_swt_forward_reference(x, levels, filt, k=None, depth_filt=None):
+    """`levels` levels of the f64acc per-axis composition (tests/volume_swt_ref.py, double=True) with `filt` on all three axes: its
+    1 + 7 levels bands in `num` order, and per band (tolerance, noise) with noise = max |fp32 composition - f64acc composition|."""
+    k = K if k is None else k
+    ref = volume_swt_ref.forward(x, None, levels, True, filt=filt, depth_filt=depth_filt)
+    f32 = volume_swt_ref.forward(x, None, levels, False, filt=filt, depth_filt=depth_filt)
+    return ref, [_tol(r, f, k) for r, f in zip(ref, f32)]
+
+
+def volume_swt_inverse_reference(bands, levels, filt, k=None, depth_filt=None):
+    """The f64acc composition's synthesis of `bands` (fp32 arrays, e.g. volume_swt_forward_reference's), and its (tolerance, noise)."""
+    k = K if k is None else k
+    ref = volume_swt_ref.inverse(bands, None, levels, True, filt=filt, depth_filt=depth_filt)
+    f32 = volume_swt_ref.inverse(bands, None, levels, False, filt=filt, depth_filt=depth_filt)
+    return ref, _tol(ref, f32, k)
+
+
+def swt_depth_tap_factor(x, levels, filt, which, j, ref, tols, iref=None, itol=None):
+    """Zeroing tap j of filter `which` in the DEPTH steps alone moves the f64acc composition by this many tolerances.  dec_lo (1) /
+    dec_hi (2): the forward of x, in the band it moves most; ref, tols: volume_swt_forward_reference(x, levels, filt).  rec_lo (3) /
+    rec_hi (4): the inverse of `ref`, the reference's own bands; iref, itol: volume_swt_inverse_reference(ref, levels, filt)."""
+    cut = without_tap(filt, which, j)
+    if which in (1, 2):
+        got = volume_swt_ref.forward(x, None, levels, True, filt=filt, depth_filt=cut)
+        return max(float(np.abs(g.astype(np.float64) - r).max()) / tol for g, r, (tol, _) in zip(got, ref, tols))
+    got = volume_swt_ref.inverse(ref, None, levels, True, filt=filt, depth_filt=cut)
+    return float(np.abs(got.astype(np.float64) - iref).max()) / itol

@@ -31,7 +31,7 @@ def header_functions(which=("pypwt_amd.h", "pypwt_amd_bench.h")):
 
 BENCH_ONLY = {"pdwt_fill_image_hash", "pdwt_enable_kernel_timing", "pdwt_kernel_times", "pdwt_reset_kernel_times", "pdwt_time_level",
               "pdwt_time_copy", "pdwt_copy_capacity", "pdwt_schedule_string", "pdwt_set_tuning", "pdwt_kernel_families",
-              "pdwt_volume_set_filters", "pdwt_volume_set_depth_segments"}
+              "pdwt_volume_set_filters", "pdwt_volume_set_depth_segments", "pdwt_volume_depth_width"}
 
 
 def test_the_contract_header_holds_no_measurement_hook():
@@ -113,6 +113,8 @@ def test_argument_errors_without_gpu(lib):
     assert lib.pdwt_create(p, 0, 8, b"db2", 1, 1, 1, 0, 0, 2, C.byref(h)) == _lib.ERR_ARG
     assert lib.pdwt_forward(None) == _lib.ERR_ARG
     assert lib.pdwt_destroy(None) == 0
+    for inverse in (0, 1):  # the test hook of a volume's depth widths: a null handle is an argument error, not a width
+        assert lib.pdwt_volume_depth_width(None, 1, inverse) == _lib.ERR_ARG
 
 
 def test_no_gpu_means_loud_failure_not_fallback(lib):

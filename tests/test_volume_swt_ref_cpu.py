@@ -7,6 +7,8 @@ three sides, on the CPU:
     cases have small-integer inputs, a fifth small one (c4) has real-valued data and coefficients;
   * to the committed oracle: its y and x steps alone on an image are the oracle's 2D SWT, three levels, both directions, 1e-12;
   * to itself: the round trip on odd sizes, which pywt refuses, to 1e-12.
+  * its f64acc mode (double=True: fp32 data and taps, one rounding per axis step -- the reference of tests/tap_banks.py's stationary
+    helpers) to the fp64 one, on the golden cases, at a bound counted from the roundings and the filters' L1 norms.
 
 The last test is about the resolving power of tests/test_gpu_volume_swt.py: zeroing ANY single tap of any of the four filters in
 the depth step alone moves the composition by at least 1000 x the tolerance the GPU module compares at (in the band it moves
@@ -109,6 +111,57 @@ def test_fp32_mode_is_fp32_throughout_and_near_the_fp64_one():
     assert all(b.dtype == np.float32 for b in b32) and all(b.dtype == np.float64 for b in b64)
     assert max(float(np.abs(a - b).max()) for a, b in zip(b32, b64)) <= 1e-5 * 255.0 * 4
     assert ref.inverse(b32, "db2", 1, False).dtype == np.float32
+
+
+U32 = 2.0 ** -24  # the relative error of one rounding to fp32
+
+
+@pytest.mark.parametrize("case", ["c0", "c1", "c2", "c3", "c4"])
+def test_f64acc_mode_is_one_rounding_per_axis_step_away_from_the_fp64_one(case):
+    """double=True: fp32 data and taps, every axis step summed in fp64 and rounded to fp32 once.  Compared with "full" on the same
+    fp32 input and the same fp32 taps (exact in fp64), so the roundings of the steps are all that differs.
+
+    The bound.  N = the largest L1 norm of the two filters of a direction (the synthesis: (|rec_lo|_1 + |rec_hi|_1) / 2, its two
+    half sums share one rounding), M = max |input|.  After s axis steps every exact value is at most N^s M; step s rounds a value of
+    at most that size (error <= u N^s M, u = 2^-24) and carries the earlier error through a filter (factor N):
+    e_s <= N e_(s-1) + u N^s M, so e_s <= s u N^s M.  L levels are s = 3 L steps; one more u N^s M covers what the recursion
+    drops -- the fp64 sums' own error (hlen 2^-53 per step) and the growth (1 + u)^s of the rounded values: (3 L + 1) u N^(3 L) M."""
+    x64, wname, levels, _, coef64, _ = golden()[case]
+    x = x64.astype(np.float32)
+    filt = tuple(oracle.filters(wname, np.float32))
+    acc, full = ref.forward(x, None, levels, True, filt=filt), ref.forward(x, None, levels, "full", filt=filt)
+    f32 = ref.forward(x, None, levels, False, filt=filt)
+    l1 = [float(np.abs(np.asarray(t, dtype=np.float64)).sum()) for t in filt[1:5]]
+    steps = 3 * levels
+    bound = (steps + 1) * U32 * max(l1[0], l1[1]) ** steps * float(np.abs(x).max())
+    worst = 0.0
+    for num, (a, f) in enumerate(zip(acc, full)):
+        assert a.dtype == np.float32 and f.dtype == np.float64 and a.shape == f.shape == x.shape
+        worst = max(worst, float(np.abs(a.astype(np.float64) - f).max()))
+        assert float(np.abs(a.astype(np.float64) - f).max()) <= bound, (case, num, bound)
+    coef = [c.astype(np.float32) for c in coef64]
+    iacc, ifull = ref.inverse(coef, None, levels, True, filt=filt), ref.inverse(coef, None, levels, "full", filt=filt)
+    ibound = (steps + 1) * U32 * (0.5 * (l1[2] + l1[3])) ** steps * max(float(np.abs(c).max()) for c in coef)
+    ierr = float(np.abs(iacc.astype(np.float64) - ifull).max())
+    assert iacc.dtype == np.float32 and ierr <= ibound, (case, ierr, ibound)
+    print("f64acc %s: forward %.3g of %.3g, inverse %.3g of %.3g" % (case, worst, bound, ierr, ibound))
+    # ONE axis step is the fp64 step rounded, bit for bit (the same sums in the same order), and nothing of "full" or False moved
+    lo, hi = ref.analysis_axis(x, filt[1], filt[2], 1, 0, True)
+    wlo, whi = ref.analysis_axis(x.astype(np.float64), filt[1].astype(np.float64), filt[2].astype(np.float64), 1, 0)
+    assert np.array_equal(lo, wlo.astype(np.float32)) and np.array_equal(hi, whi.astype(np.float32))
+    back = ref.synthesis_axis(lo, hi, filt[3], filt[4], 1, 0, True)
+    wide = ref.synthesis_axis(lo.astype(np.float64), hi.astype(np.float64), filt[3].astype(np.float64), filt[4].astype(np.float64), 1, 0)
+    assert np.array_equal(back, wide.astype(np.float32))
+    # the fp32 mode rounds every product and sum: where it differs from the fp64 one at all, it is no closer than the f64acc mode
+    e32 = max(float(np.abs(a.astype(np.float64) - f).max()) for a, f in zip(f32, full))
+    assert worst <= e32 or e32 == 0.0, (case, worst, e32)
+
+
+def test_the_modes_are_full_true_and_false_and_nothing_else():
+    x = np.zeros((2, 2, 2), dtype=np.float32)
+    for bad in ("f64acc", 2, None, "True"):
+        with pytest.raises(ValueError):
+            ref.forward(x, "haar", 1, bad)
 
 
 def test_thresholds_are_ops_refs_per_level():

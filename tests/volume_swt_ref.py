@@ -11,7 +11,9 @@ Also here: band numbering and shapes of a stationary pdwt_volume (include/pypwt_
 band of the volume's own shape --, the level clamp, and the thresholds through tests/ops_ref.py.
 
 `double`: "full" -- fp64 data and arithmetic; False -- fp32 data and arithmetic (every product and sum rounds to fp32; the stack
-between the depth step and the 2D step is fp32, as on the device).
+between the depth step and the 2D step is fp32, as on the device); True -- fp32 data and fp32 taps, every axis step accumulated in
+fp64 and rounded to fp32 ONCE per step (so the volume between the depth step and the 2D steps is fp32 here too): the meaning
+double=True has in tests/volume_ref.py, and the reference tests/tap_banks.py measures a correct fp32 evaluation's noise against.
 
 `filt` = (hlen, dec_lo, dec_hi, rec_lo, rec_hi) replaces the named wavelet's bank on all three axes; `depth_filt` is a bank for
 the depth step alone.
@@ -24,9 +26,13 @@ from volume_ref import KEYS, SUB, clamp_levels, hlen_of, num_of  # noqa: F401  (
 
 
 def _dtype(double):
-    if double not in ("full", False):
-        raise ValueError("volume_swt_ref: double must be 'full' or False")
+    if not (isinstance(double, str) and double == "full") and double not in (False, True):
+        raise ValueError("volume_swt_ref: double must be 'full', True or False")
     return np.float64 if double == "full" else np.float32
+
+
+def _f64acc(double):
+    return not isinstance(double, str) and bool(double)
 
 
 def bank(wname, double, filt=None):
@@ -37,8 +43,33 @@ def bank(wname, double, filt=None):
     return (int(filt[0]),) + tuple(np.ascontiguousarray(t, dtype=dt) for t in filt[1:5])
 
 
-def analysis_axis(x, lo, hi, level, axis):
-    """One undecimated analysis step along `axis`: (low, high), both of x's shape and type."""
+def _f64acc_analysis(x, lo, hi, level, axis):
+    """analysis_axis with every sum in fp64 -- the products of two fp32 values are exact there -- and ONE rounding to x's type."""
+    hlen, f, c = len(lo), 1 << (level - 1), len(lo) // 2 - 1
+    wide = x.astype(np.float64)
+    aL, aH = np.zeros_like(wide), np.zeros_like(wide)
+    for j in range(hlen):
+        v = np.roll(wide, -(j - c) * f, axis=axis)
+        aL = aL + v * np.float64(lo[hlen - 1 - j])
+        aH = aH + v * np.float64(hi[hlen - 1 - j])
+    return aL.astype(x.dtype), aH.astype(x.dtype)
+
+
+def _f64acc_synthesis(a, d, rlo, rhi, level, axis):
+    """synthesis_axis with every sum in fp64 (the halving is exact) and ONE rounding to a's type."""
+    hlen, f, c = len(rlo), 1 << (level - 1), len(rlo) // 2
+    wa, wd = a.astype(np.float64), d.astype(np.float64)
+    ra, rd = np.zeros_like(wa), np.zeros_like(wd)
+    for j in range(hlen):
+        ra = ra + np.roll(wa, -(j - c) * f, axis=axis) * np.float64(rlo[hlen - 1 - j]) / 2.0
+        rd = rd + np.roll(wd, -(j - c) * f, axis=axis) * np.float64(rhi[hlen - 1 - j]) / 2.0
+    return (ra + rd).astype(a.dtype)
+
+
+def analysis_axis(x, lo, hi, level, axis, f64acc=False):
+    """One undecimated analysis step along `axis`: (low, high), both of x's shape and type; `f64acc`: summed in fp64, rounded once."""
+    if f64acc:
+        return _f64acc_analysis(x, lo, hi, level, axis)
     hlen, f, c = len(lo), 1 << (level - 1), len(lo) // 2 - 1
     dt = x.dtype.type
     aL, aH = np.zeros_like(x), np.zeros_like(x)
@@ -49,8 +80,10 @@ def analysis_axis(x, lo, hi, level, axis):
     return aL, aH
 
 
-def synthesis_axis(a, d, rlo, rhi, level, axis):
+def synthesis_axis(a, d, rlo, rhi, level, axis, f64acc=False):
     """One undecimated synthesis step along `axis`; the factor 1/2 sits inside the sum (pdwt_oracle.c:253-254)."""
+    if f64acc:
+        return _f64acc_synthesis(a, d, rlo, rhi, level, axis)
     hlen, f, c = len(rlo), 1 << (level - 1), len(rlo) // 2
     dt = a.dtype.type
     ra, rd = np.zeros_like(a), np.zeros_like(d)
@@ -60,27 +93,27 @@ def synthesis_axis(a, d, rlo, rhi, level, axis):
     return ra + rd
 
 
-def forward_level(a, level, filt, depth_filt=None):
+def forward_level(a, level, filt, depth_filt=None, f64acc=False):
     """{key: band} with all eight keys of one level at dilation 2^(level - 1); key = (z, y, x) letters, 'a' low, 'd' high."""
     depth_filt = depth_filt or filt
     out = {"": a}
     for axis, fb in ((0, depth_filt), (1, filt), (2, filt)):
         nxt = {}
         for key, band in out.items():
-            lo, hi = analysis_axis(band, fb[1], fb[2], level, axis)
+            lo, hi = analysis_axis(band, fb[1], fb[2], level, axis, f64acc)
             nxt[key + "a"], nxt[key + "d"] = lo, hi
         out = nxt
     return out
 
 
-def inverse_level(bands, level, filt, depth_filt=None):
+def inverse_level(bands, level, filt, depth_filt=None, f64acc=False):
     """{key: band} with all eight keys -> the approximation one level up: x, then y (the device's 2D inverse), then z."""
     depth_filt = depth_filt or filt
     cur = dict(bands)
     for axis, fb in ((2, filt), (1, filt), (0, depth_filt)):
         nxt = {}
         for key in {k[:-1] for k in cur}:
-            nxt[key] = synthesis_axis(cur[key + "a"], cur[key + "d"], fb[3], fb[4], level, axis)
+            nxt[key] = synthesis_axis(cur[key + "a"], cur[key + "d"], fb[3], fb[4], level, axis, f64acc)
         cur = nxt
     return cur[""]
 
@@ -92,7 +125,7 @@ def forward(vol, wname, levels, double="full", filt=None, depth_filt=None):
     a = np.ascontiguousarray(vol, dtype=_dtype(double))
     details = []
     for l in range(1, levels + 1):
-        lv = forward_level(a, l, fb, dfb)
+        lv = forward_level(a, l, fb, dfb, _f64acc(double))
         details += [lv[k] for k in KEYS]
         a = lv["aaa"]
     return [a] + details
@@ -106,7 +139,7 @@ def inverse(bands, wname, levels, double="full", filt=None, depth_filt=None):
     for l in range(levels, 0, -1):
         lv = {k: np.ascontiguousarray(bands[num_of(l, k)], dtype=dt) for k in KEYS}
         lv["aaa"] = a
-        a = inverse_level(lv, l, fb, dfb)
+        a = inverse_level(lv, l, fb, dfb, _f64acc(double))
     return a
 
 
