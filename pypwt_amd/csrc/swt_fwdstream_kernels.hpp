@@ -40,10 +40,24 @@ struct SwtFwdStreamArgs {
 // of whole groups (Nc % 4 == 0): the groups are aligned, pad = x0 mod 4.  Any other width: the groups are loaded at 4-B alignment, and
 // none may straddle the row end -- where the staged window [x0, x0 + xs) runs past the END of the row the groups are laid out from
 // there backwards (pad = (x0 - Nc) mod 4), where it starts before column 0 from 0 (the same formula as the aligned case); a window
-// that does both needs Nc % 4 == 0 (the launcher declines narrower images of other widths).
+// that does both needs Nc % 4 == 0 (the launcher declines narrower images of other widths).  "Runs past the end" is said of the
+// GROUPS, not of the window: a window that ends up to 3 samples in front of the row end, or at it, has its last group across the end
+// when the groups are laid out from column 0 (6 taps, 131 columns, strip 1: columns 126 ... 194 in groups from 124 -- the last one
+// is 192 ... 195); laid out backwards from the end none does.  Rows of whole groups: both tests are the same.
 PDWT_DEVICE int swt_stage_pad(int x0, int xs, int Nc) {
-    const bool right_only = x0 >= 0 && x0 + xs > Nc;
-    return true_mod(right_only ? x0 - Nc : x0, 4);
+    const int pad0 = true_mod(x0, 4);
+    const bool right_only = x0 >= 0 && x0 - pad0 + (pad0 + xs + 3) / 4 * 4 > Nc;
+    return right_only ? true_mod(x0 - Nc, 4) : pad0;
+}
+
+// Source column of group g of a staged row.  A row's groups are numbered by the compile-time count NQ = (xs + 6) / 4 (pad = 3), but
+// only the first ceil((pad + xs) / 4) of them reach into the window [x0, x0 + xs), and swt_stage_pad keeps only THOSE inside the
+// row: a surplus group of a row that is not whole groups could start before column Nc and end behind it -- behind the plane, on the
+// last row of the last image.  A surplus group therefore loads the last needed group again (the staging discards its samples: they
+// lie at or behind xs).  Computed once per workgroup, in the plan: nothing is added to the loads of a step.
+PDWT_DEVICE int swt_stage_col(int x0, int pad, int xs, int g, int Nc) {
+    const int last = (pad + xs + 3) / 4 - 1;
+    return wrap_periodic(x0 - pad + 4 * (g < last ? g : last), Nc);
 }
 
 template <int HLEN, int F, int TXC, int TY>
@@ -89,7 +103,6 @@ PDWT_DEVICE void swt_fwdstream_wg(const SwtFwdStreamArgs& a, int strip, int py, 
     const int T = W + (nm + TY - 1) / TY;
     const int pbase = i0 - C + D - W * TY;   // chain position of the first row of step 0
     const int padl = swt_stage_pad(k0 - C * F, XS, a.Nc);
-    const int xa = k0 - C * F - padl;        // the origin of the row's 16-B groups
     const long long boff = (long long)bz * a.bstride;
     const real_t* PDWT_RESTRICT in = a.in + boff;
     const LanePlane pA = lane_plane(a.A + boff), pH = lane_plane(a.H + boff), pV = lane_plane(a.V + boff), pD = lane_plane(a.D + boff);
@@ -110,7 +123,7 @@ PDWT_DEVICE void swt_fwdstream_wg(const SwtFwdStreamArgs& a, int strip, int py, 
             const int g = idx - r * NQ;
             pl[4 * q + 0] = r * RXA;
             pl[4 * q + 1] = 4 * g - padl;
-            pl[4 * q + 2] = wrap_periodic(xa + 4 * g, a.Nc);  // a group never straddles the row end (swt_stage_pad)
+            pl[4 * q + 2] = swt_stage_col(k0 - C * F, padl, XS, g, a.Nc);  // no group straddles the row end (swt_stage_pad, swt_stage_col)
             pl[4 * q + 3] = true_mod(pbase + r, rows_phase);
         }
     };

@@ -73,7 +73,6 @@ PDWT_DEVICE void swt_invstream_wg(const SwtInvStreamArgs& a, int strip, int py, 
     const int T = W + (nm + TY - 1) / TY;
     const int pbase = i0 - C + D - W * TY;
     const int padl = swt_stage_pad(k0 - C * F, XS, a.Nc);
-    const int xa = k0 - C * F - padl;
     const long long boff = (long long)bz * a.bstride;
     const real_t* PDWT_RESTRICT pA = a.A + boff;
     const real_t* PDWT_RESTRICT pH = a.H + boff;
@@ -102,7 +101,7 @@ PDWT_DEVICE void swt_invstream_wg(const SwtInvStreamArgs& a, int strip, int py, 
             idx = idx < TOTAL ? idx : TOTAL - 1;
             const int r = idx / NQ;
             const int g = idx - r * NQ;
-            pl[2 * q + 0] = wrap_periodic(xa + 4 * g, a.Nc);
+            pl[2 * q + 0] = swt_stage_col(k0 - C * F, padl, XS, g, a.Nc);  // (a surplus group: the last needed one again)
             pl[2 * q + 1] = true_mod(pbase + r, rows_phase);
         }
     };

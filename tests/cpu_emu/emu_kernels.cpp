@@ -1,11 +1,7 @@
 // CPU emulation build of the gfx950 tile functions (sanitizer / index-math fuzz only).
 // Compiles pypwt_amd/csrc/*_kernels.hpp with PDWT_CPU_EMU: phases run as loops over
 // thread ids, blocks as loops over the grid.  Test infrastructure; never shipped.
-#define PDWT_CPU_EMU 1
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "emu_common.hpp"
 
 #include "../../pypwt_amd/csrc/dwt1_fused_kernels.hpp"
 #include "../../pypwt_amd/csrc/dwt1_kernels.hpp"
@@ -34,20 +30,6 @@
 #include "../../pypwt_amd/csrc/dwt2_stream_kernels.hpp"
 #include "../../pypwt_amd/csrc/dwt2_split_kernels.hpp"
 #include "../../pypwt_amd/csrc/lazy_state.hpp"
-
-using namespace pdwt;
-
-#define EMU_API extern "C" __attribute__((visibility("default")))
-
-static void set_bank(FilterBank& fb, const float* lo, const float* hi, int hlen) {
-    std::memset(&fb, 0, sizeof(fb));
-    for (int i = 0; i < hlen; i++) { fb.lo[i] = lo[i]; fb.hi[i] = hi[i]; }
-}
-
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-#define EMU_EVEN_HLENS(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) \
-    X(28) X(30) X(32) X(34) X(36) X(38) X(40)
 
 template <int HLEN, int TX, int TY, int NT>
 static void run_fwd2d(const Fwd2DArgs& a, int batch) {
@@ -224,95 +206,7 @@ EMU_API int emu_swt_pass(int inverse, const float* in0, const float* in1, int Nr
 }
 
 // ------------------------------------------------------------------ tuned 2D kernels
-static void set_bank_i(FilterBankI& fb, const float* lo, const float* hi, int hlen) {
-    std::memset(&fb, 0, sizeof(fb));
-    for (int i = 0; i < hlen; i++) { fb.t[i].x = lo[i]; fb.t[i].y = hi[i]; }
-}
-
-template <int HLEN, int TX, int TY, int NT>
-static void run_fwd2d_fast(Fwd2DFastArgs a, int batch) {
-    std::vector<float> smem(fwd2d_fast_lds_floats<HLEN, TX, TY>() + 64, -12345.f);
-    a.tiles_x = cdiv(a.Nc2, TX); a.tiles_y = cdiv(a.Nr2, TY);
-    const int chunk = (a.tiles_x * a.tiles_y + 7) / 8;
-    std::vector<int> seen(a.tiles_x * a.tiles_y, 0);
-    for (int bz = 0; bz < batch; bz++)
-        for (int b = 0; b < 8 * chunk; b++) {
-            int bx, by;
-            if (!xcd_tile(b, a.tiles_x, a.tiles_y, bx, by)) continue;
-            if (bz == 0) seen[by * a.tiles_x + bx]++;
-            dwt2_fwd_fast_tile<HLEN, TX, TY, NT>(a, bx, by, bz, smem.data());
-        }
-    for (int v : seen) if (v != 1) std::abort();  // the XCD renumbering must be a bijection
-}
-
-template <int HLEN, int TX, int TY, int NT>
-static void run_inv2d_fast(Inv2DFastArgs a, int batch) {
-    std::vector<float> smem(inv2d_fast_lds_floats<HLEN, TX, TY>() + 64, -12345.f);
-    a.tiles_x = cdiv(a.Nc, 2 * TX); a.tiles_y = cdiv(a.Nr, 2 * TY);
-    const int chunk = (a.tiles_x * a.tiles_y + 7) / 8;
-    for (int bz = 0; bz < batch; bz++)
-        for (int b = 0; b < 8 * chunk; b++) {
-            int bx, by;
-            if (!xcd_tile(b, a.tiles_x, a.tiles_y, bx, by)) continue;
-            dwt2_inv_fast_tile<HLEN, TX, TY, NT>(a, bx, by, bz, smem.data());
-        }
-}
-
-template <int HLEN, int TX, int TY, int NT>
-static void run_fwd2d_stream(Fwd2DFastArgs a, int batch, int nwg) {
-    std::vector<float> smem(fwd2d_fast_lds_floats<HLEN, TX, TY>() + 64, -12345.f);
-    a.tiles_x = cdiv(a.Nc2, TX); a.tiles_y = cdiv(a.Nr2, TY);
-    for (int wg = 0; wg < nwg; wg++) dwt2_fwd_fast_stream<HLEN, TX, TY, NT>(a, wg, nwg, batch, smem.data());
-}
-
-// nwg: number of persistent workgroups (multiple of 8)
-EMU_API int emu_dwt2_fwd_stream(const float* in, int batch, int Nr, int Nc, const float* lo, const float* hi, int hlen,
-                                int nwg, float* A, float* H, float* V, float* D) {
-    if ((hlen & 1) || (Nc & 3) || (nwg & 7)) return -2;
-    Fwd2DFastArgs a;
-    a.in = in; a.A = A; a.H = H; a.V = V; a.D = D;
-    a.Nr = Nr; a.Nc = Nc; a.Nr2 = (Nr + 1) / 2; a.Nc2 = Nc / 2;
-    a.in_bstride = (long long)Nr * Nc; a.out_bstride = (long long)a.Nr2 * a.Nc2;
-    set_bank_i(a.fb, lo, hi, hlen);
-    switch (hlen) {
-#define X(h) case h: run_fwd2d_stream<h, 64, 8, 256>(a, batch, nwg); return 0;
-        EMU_EVEN_HLENS(X)
-#undef X
-    }
-    return -1;
-}
-
-EMU_API int emu_dwt2_fwd_fast(const float* in, int batch, int Nr, int Nc, const float* lo, const float* hi, int hlen,
-                              int tile, float* A, float* H, float* V, float* D) {
-    if (hlen & 1) return -2;  // any width: rows that are not whole quads take the unaligned staging / element stores
-    Fwd2DFastArgs a;
-    a.in = in; a.A = A; a.H = H; a.V = V; a.D = D;
-    a.Nr = Nr; a.Nc = Nc; a.Nr2 = (Nr + 1) / 2; a.Nc2 = (Nc + 1) / 2;
-    a.in_bstride = (long long)Nr * Nc; a.out_bstride = (long long)a.Nr2 * a.Nc2;
-    set_bank_i(a.fb, lo, hi, hlen);
-    switch (hlen) {
-#define X(h) case h: if (tile == 0) run_fwd2d_fast<h, 64, 16, 256>(a, batch); else if (tile == 1) run_fwd2d_fast<h, 64, 32, 512>(a, batch); else run_fwd2d_fast<h, 64, 32, 256>(a, batch); return 0;
-        EMU_EVEN_HLENS(X)
-#undef X
-    }
-    return -1;
-}
-
-EMU_API int emu_dwt2_inv_fast(const float* A, const float* H, const float* V, const float* D, int batch, int Nrc,
-                              int Ncc, int Nr, int Nc, const float* lo, const float* hi, int hlen, int tile, float* out) {
-    if ((hlen & 1) || Nc > 2 * Ncc || Nc < 2 * Ncc - 1) return -2;
-    Inv2DFastArgs a;
-    a.A = A; a.H = H; a.V = V; a.D = D; a.out = out;
-    a.Nrc = Nrc; a.Ncc = Ncc; a.Nr = Nr; a.Nc = Nc;
-    a.in_bstride = (long long)Nrc * Ncc; a.out_bstride = (long long)Nr * Nc;
-    set_bank_i(a.fb, lo, hi, hlen);
-    switch (hlen) {
-#define X(h) case h: if (tile == 0) run_inv2d_fast<h, 64, 16, 256>(a, batch); else if (tile == 1) run_inv2d_fast<h, 64, 8, 256>(a, batch); else run_inv2d_fast<h, 64, 32, 512>(a, batch); return 0;
-        EMU_EVEN_HLENS(X)
-#undef X
-    }
-    return -1;
-}
+#include "emu_dwt2_fast.inc"
 
 // ------------------------------------------------------------------ non-separable
 // filt: 4 banks of hlen*hlen ; inverse != 0: A..D inputs, io output
@@ -667,11 +561,6 @@ EMU_API int emu_dwt2_inv_strip2(const float* l1, const float* l2, int batch, int
 }
 
 // ------------------------------------------------------------------ wave-per-tile 2D level kernels
-static void interleave_bank(FilterBankI& o, const float* lo, const float* hi, int hlen) {
-    std::memset(&o, 0, sizeof(o));
-    for (int i = 0; i < hlen; i++) { o.t[i].x = lo[i]; o.t[i].y = hi[i]; }
-}
-
 template <int HLEN>
 static void run_fwd_wave(const FwdWaveArgs& a, int batch, int guard) {
     for (int bz = 0; bz < batch; bz++)
@@ -878,119 +767,13 @@ EMU_API int emu_dwt1_inv_reg(const float* app, const float* det, int rows, int N
     return -1;
 }
 
-// ------------------------------------------------------------------ 2D SWT, 2-tap filters, two or three levels per launch
-template <int K, int F0>
-static void run_swt_fused(SwtFusedArgs& a, int batch, bool inverse, int cpl) {
-    // sizes the aligned instantiations cannot take run the GEN ones (SwtWalk); `cpl` + 8 forces them on every size
-    const bool gen = swt_walk_general(a.Nr, a.Nc, F0) || cpl >= 8;
-    cpl &= 7;
-    a.wk = swt_walk(a.Nr, a.Nc, F0, inverse ? cpl : 4);
-    if (inverse) a.strips = cpl == 2 ? swt_walk_strips(a.wk, a.Nc, 2 * SwtInvGeom<K, F0, 2>::V) : swt_walk_strips(a.wk, a.Nc, 4 * SwtInvGeom<K, F0, 4>::V);
-    else a.strips = swt_walk_strips(a.wk, a.Nc, 4 * SwtFusedGeom<K, F0>::V);
-    a.segs = (a.wk.rows_phase + a.seg_rows - 1) / a.seg_rows;
-    const long long waves = (long long)batch * a.wk.phases * a.segs * a.strips;
-    for (long long w = 0; w < waves; w++) {
-        if (!inverse) { if (gen) swt2_fwd_fused<K, F0, true>(a, w); else swt2_fwd_fused<K, F0, false>(a, w); }
-        else if (cpl == 2) { if (gen) swt2_inv_fused<K, F0, 4, 2, true>(a, w); else swt2_inv_fused<K, F0, 4, 2, false>(a, w); }
-        else { if (gen) swt2_inv_fused<K, F0, 4, 4, true>(a, w); else swt2_inv_fused<K, F0, 4, 4, false>(a, w); }
-    }
-}
-
-// planes: forward  in -> det (K x [H, V, D] planes, level l0 first) and out;  inverse  in (A) + det -> out
-EMU_API int emu_swt2_fused(const float* in, float* det, float* out, int batch, int Nr, int Nc, int K, int f0, int seg_rows,
-                           const float* lo, const float* hi, const float* beta, int inverse, int cpl) {
-    if (K < 2 || K > 3 || (f0 != 1 && f0 != 8) || Nc < 256 || Nr / f0 < (1 << K) || seg_rows % (1 << K)) return -2;
-    SwtFusedArgs a;
-    const long long plane = (long long)Nr * Nc;
-    a.in = in; a.out = out; a.Nr = Nr; a.Nc = Nc; a.bstride = plane;
-    for (int k = 0; k < kSwtFusedMaxLevels; k++) {
-        a.H[k] = a.V[k] = a.D[k] = nullptr;
-        a.beta[k] = (beta && k < K) ? beta[k] : 0.f;
-    }
-    for (int k = 0; k < K; k++) {
-        a.H[k] = det + (3 * k + 0) * batch * plane;
-        a.V[k] = det + (3 * k + 1) * batch * plane;
-        a.D[k] = det + (3 * k + 2) * batch * plane;
-    }
-    a.lo[0] = lo[0]; a.lo[1] = lo[1]; a.hi[0] = hi[0]; a.hi[1] = hi[1];
-    a.seg_rows = seg_rows;
-    a.segs = (Nr / f0 + seg_rows - 1) / seg_rows;
-#define Y(k, f) if (K == k && f0 == f) { run_swt_fused<k, f>(a, batch, inverse != 0, cpl); return 0; }
-    Y(2, 1) Y(3, 1) Y(2, 8) Y(3, 8)
-#undef Y
-    return -1;
-}
-
-// ---- 4-tap fused SWT pairs (swt2_fused4_kernels.hpp): planes as in emu_swt2_fused with K = 2
-template <int F0>
-static void run_swt4(Swt4Args& a, int batch, bool inverse, bool gen) {
-    using G = Swt4Geom<F0>;
-    const int V = inverse ? G::Vi : G::Vf;
-    a.wk = swt_walk(a.Nr, a.Nc, F0, 4);
-    a.strips = swt_walk_strips(a.wk, a.Nc, 4 * V);
-    a.segs = (a.wk.rows_phase + a.seg_rows - 1) / a.seg_rows;
-    const long long waves = (long long)batch * a.wk.phases * a.segs * a.strips;
-    for (long long w = 0; w < waves; w++) {
-        if (!inverse) { if (gen) swt4_fwd_fused<F0, true>(a, w); else swt4_fwd_fused<F0, false>(a, w); }
-        else { if (gen) swt4_inv_fused<F0, 4, true>(a, w); else swt4_inv_fused<F0, 4, false>(a, w); }
-    }
-}
-
-EMU_API int emu_swt4_fused(const float* in, float* det, float* out, int batch, int Nr, int Nc, int f0, int seg_rows,
-                           const float* lo, const float* hi, const float* beta, int inverse) {
-    const bool gen = swt_walk_general(Nr, Nc, f0) || (inverse & 2);  // inverse + 2: the GEN instantiations on every size
-    if ((f0 != 1 && f0 != 4) || Nc < (gen ? 256 : 64) || Nr / f0 < 8 || seg_rows % 8) return -2;
-    Swt4Args a;
-    const long long plane = (long long)Nr * Nc;
-    a.in = in; a.out = out; a.Nr = Nr; a.Nc = Nc; a.bstride = plane;
-    for (int k = 0; k < 2; k++) {
-        a.H[k] = det + (3 * k + 0) * batch * plane;
-        a.V[k] = det + (3 * k + 1) * batch * plane;
-        a.D[k] = det + (3 * k + 2) * batch * plane;
-        a.beta[k] = beta ? beta[k] : 0.f;
-    }
-    for (int j = 0; j < 4; j++) { a.lo[j] = lo[j]; a.hi[j] = hi[j]; }
-    a.seg_rows = seg_rows;
-    a.segs = (Nr / f0 + seg_rows - 1) / seg_rows;
-    if (f0 == 1) run_swt4<1>(a, batch, (inverse & 1) != 0, gen);
-    else run_swt4<4>(a, batch, (inverse & 1) != 0, gen);
-    return 0;
-}
-
-// the column pass streamed down strips (swt_colstream_kernels.hpp) on the arguments of the register column kernels
-static int g_colstream_runs = 0;
-EMU_API int emu_colstream_runs() { return g_colstream_runs; }  // launches that took the strip kernels so far
-template <int HLEN, bool INV>
-static bool run_swt_colstream(const SwtSplitArgs& c) {
-    if constexpr (HLEN < 10) {
-        return false;
-    } else {
-        constexpr int TXC = 64, TY = 32, NT = 256, M = 8;
-        using G = SwtColStreamGeom<HLEN, INV, TXC, TY>;
-        SwtColStreamArgs a;
-        for (int k = 0; k < 4; ++k) { a.in[k] = c.in[k]; a.out[k] = c.out[k]; }
-        a.Nr = c.Nr; a.Nc = c.Nc; a.f = c.f; a.in_bstride = c.in_bstride; a.out_bstride = c.out_bstride;
-        a.soft_beta = c.soft_beta; a.t = c.t;
-        a.wk = swt_walk(c.Nr, c.Nc, c.f, 4);
-        if ((c.Nc & 3) || a.wk.rows_phase < TY) return false;
-        a.strips = (c.Nc + TXC - 1) / TXC;
-        const char* e = getenv("EMU_COLSTREAM_SEG");  // rows of a chain per segment (default: two segments)
-        int seg = e ? atoi(e) : (a.wk.rows_phase + 1) / 2;
-        a.seg = (seg + TY - 1) / TY * TY;
-        a.segs = (a.wk.rows_phase + a.seg - 1) / a.seg;
-        std::vector<float> smem(G::LDS_REALS, NAN);
-        ++g_colstream_runs;
-        for (int bz = 0; bz < c.batch; ++bz)
-            for (int py = 0; py < a.wk.phases; ++py)
-                for (int sg = 0; sg < a.segs; ++sg)
-                    for (int st = 0; st < a.strips; ++st) swt_colstream_wg<HLEN, INV, TXC, TY, NT, M>(a, st, py, sg, bz, smem.data());
-        return true;
-    }
-}
+#include "emu_swt_fused.inc"
 
 // ---- host-side geometry of the strip walks and of the any-size fused groups (pure functions)
 EMU_API int emu_strip_walk_seg(int rows, long long units, int ty, int warm, int slots) { return strip_walk_seg(rows, units, ty, warm, slots); }
 EMU_API int emu_swt_stage_pad(int x0, int xs, int Nc) { return swt_stage_pad(x0, xs, Nc); }
+// the source column of group g of the (xs + 6) / 4 groups the one-launch SWT kernels load per staged row of the window [x0, x0 + xs)
+EMU_API int emu_swt_stage_col(int x0, int xs, int Nc, int g) { return swt_stage_col(x0, swt_stage_pad(x0, xs, Nc), xs, g, Nc); }
 EMU_API void emu_swt_walk(int Nr, int Nc, int f0, int cols_per_lane, int* out4) {
     const SwtWalk w = swt_walk(Nr, Nc, f0, cols_per_lane);
     out4[0] = w.phases; out4[1] = w.rows_phase; out4[2] = (int)w.magic; out4[3] = w.pad;
@@ -1000,137 +783,11 @@ EMU_API int emu_swt_walk_row(int Nr, int Nc, int f0, int py, int idx) {
     return swt_walk_row<true, 1>(w, Nr, py, idx * f0);
 }
 
-// ---- one forward a-trous level in ONE launch, row and column pass streamed down strips (swt_fwdstream_kernels.hpp)
-template <int HLEN, int F>
-static int run_swt_fwdstream(const float* in, float* A, float* H, float* V, float* D, int batch, int Nr, int Nc, const float* lo, const float* hi, int seg_rows) {
-    constexpr int TXC = 64, TY = F >= 8 ? 16 : 32, NT = 256, KB = F >= 8 ? 4 : 8, M = F >= 8 ? 4 : 8;
-    using G = SwtFwdStreamGeom<HLEN, F, TXC, TY>;
-    SwtFwdStreamArgs a;
-    a.in = in; a.A = A; a.H = H; a.V = V; a.D = D; a.Nr = Nr; a.Nc = Nc; a.bstride = (long long)Nr * Nc;
-    a.wk = swt_walk(Nr, Nc, F, 4);
-    if (((Nc & 3) && Nc < TXC + (HLEN - 1) * F + 4) || a.wk.rows_phase < TY) return -2;
-    for (int j = 0; j < HLEN; ++j) a.t.t[j] = mk2(lo[HLEN - 1 - j], hi[HLEN - 1 - j]);
-    a.strips = (Nc + TXC - 1) / TXC;
-    const int seg = seg_rows > 0 ? seg_rows : (a.wk.rows_phase + 1) / 2;
-    a.seg = (seg + TY - 1) / TY * TY;
-    a.segs = (a.wk.rows_phase + a.seg - 1) / a.seg;
-    std::vector<float> smem(G::LDS_REALS, NAN);
-    for (int bz = 0; bz < batch; ++bz)
-        for (int py = 0; py < a.wk.phases; ++py)
-            for (int sg = 0; sg < a.segs; ++sg)
-                for (int st = 0; st < a.strips; ++st) {
-                    std::fill(smem.begin(), smem.end(), NAN);
-                    swt_fwdstream_wg<HLEN, F, TXC, TY, NT, KB, M>(a, st, py, sg, bz, smem.data());
-                }
-    return 0;
-}
+#include "emu_swt_fwdstream.inc"
 
-EMU_API int emu_swt2_fwdstream(const float* in, int batch, int Nr, int Nc, int level, const float* lo, const float* hi, int hlen,
-                               int seg_rows, float* A, float* H, float* V, float* D) {
-    const int f = 1 << (level - 1);
-#define Y(h, ff) if (hlen == h && f == ff) return run_swt_fwdstream<h, ff>(in, A, H, V, D, batch, Nr, Nc, lo, hi, seg_rows);
-#define X(h) Y(h, 1) Y(h, 2) Y(h, 4) Y(h, 8) Y(h, 16)
-    X(6) X(8) X(10) X(12) X(16) X(20) X(26) X(40)
-#undef X
-#undef Y
-    return -1;
-}
+#include "emu_swt_invstream.inc"
 
-// ---- one inverse a-trous level in ONE launch (swt_invstream_kernels.hpp)
-template <int HLEN, int F>
-static int run_swt_invstream(const float* A, const float* H, const float* V, const float* D, float* out, int batch, int Nr, int Nc, const float* lo,
-                             const float* hi, float beta, int seg_rows) {
-    constexpr bool kShort = F >= 4 || (F == 2 && HLEN > 36);  // launch_swt_invstream.hip
-    constexpr int TXC = 64, TY = kShort ? 16 : 32, NT = 256, KB = kShort ? 4 : 8, M = kShort ? 4 : 8;
-    using G = SwtInvStreamGeom<HLEN, F, TXC, TY>;
-    SwtInvStreamArgs a;
-    a.A = A; a.H = H; a.V = V; a.D = D; a.out = out; a.Nr = Nr; a.Nc = Nc; a.bstride = (long long)Nr * Nc; a.soft_beta = beta;
-    a.wk = swt_walk(Nr, Nc, F, 4);
-    if (((Nc & 3) && Nc < TXC + (HLEN - 1) * F + 4) || a.wk.rows_phase < TY) return -2;
-    for (int j = 0; j < HLEN; ++j) a.t.t[j] = mk2(lo[HLEN - 1 - j], hi[HLEN - 1 - j]);
-    a.strips = (Nc + TXC - 1) / TXC;
-    const int seg = seg_rows > 0 ? seg_rows : (a.wk.rows_phase + 1) / 2;
-    a.seg = (seg + TY - 1) / TY * TY;
-    a.segs = (a.wk.rows_phase + a.seg - 1) / a.seg;
-    std::vector<float> smem(G::LDS_REALS, NAN);
-    for (int bz = 0; bz < batch; ++bz)
-        for (int py = 0; py < a.wk.phases; ++py)
-            for (int sg = 0; sg < a.segs; ++sg)
-                for (int st = 0; st < a.strips; ++st) {
-                    std::fill(smem.begin(), smem.end(), NAN);
-                    swt_invstream_wg<HLEN, F, TXC, TY, NT, KB, M>(a, st, py, sg, bz, smem.data());
-                }
-    return 0;
-}
-
-EMU_API int emu_swt2_invstream(const float* A, const float* H, const float* V, const float* D, int batch, int Nr, int Nc, int level, const float* lo,
-                               const float* hi, int hlen, float beta, int seg_rows, float* out) {
-    const int f = 1 << (level - 1);
-#define Y(h, ff) if (hlen == h && f == ff) return run_swt_invstream<h, ff>(A, H, V, D, out, batch, Nr, Nc, lo, hi, beta, seg_rows);
-#define X(h) Y(h, 1) Y(h, 2) Y(h, 4) Y(h, 8)
-    X(6) X(8) X(10) X(12) X(16) X(18) X(20) X(26)  // (the product builds 6-28 taps)
-#undef X
-#undef Y
-    return -1;
-}
-
-// ---- one a-trous level as a row pass + a column pass through scratch (swt_split_kernels.hpp); planes as in emu_swt2
-template <int HLEN>
-static void run_swt_split(const Swt2DArgs& a, int batch, bool inverse, float* tmp) {
-    constexpr int NT = 256, R = 4;
-    const long long plane = (long long)a.Nr * a.Nc;
-    SwtSplitArgs k{};
-    k.Nr = a.Nr; k.Nc = a.Nc; k.f = a.f; k.batch = batch; k.soft_beta = a.soft_beta;
-    for (int j = 0; j < HLEN; ++j) k.t.t[j] = mk2(a.fb.lo[HLEN - 1 - j], a.fb.hi[HLEN - 1 - j]);
-    const int f = a.f;
-    const long long col_items = split_col_waves(batch, a.Nr, a.Nc, f, R);
-    const long long row_items4 = f >= 4 ? split_row_waves(batch, a.Nr, split_row_items4(a.Nc, f, R)) : 0;
-    const long long row_lds = split_row_lds_waves(batch, a.Nr, a.Nc);
-    std::vector<float> smem(16384, NAN);  // one workgroup's LDS
-    const bool direct = getenv("EMU_SPLIT_DIRECT") != nullptr;  // dilation 4 through the kernel of the dilations >= 8 (quads f apart, no LDS)
-    const bool colstream = getenv("EMU_SPLIT_COLSTREAM") != nullptr;  // the column passes through swt_colstream_kernels.hpp
-    auto blocks = [](long long waves) { return (waves + NT / 64 - 1) / (NT / 64); };
-    if (!inverse) {
-        SwtSplitArgs r = k;
-        r.in[0] = a.in; r.in_bstride = a.bstride; r.out[0] = tmp; r.out[1] = tmp + plane; r.out_bstride = 2 * plane;
-        if (f == 1) for (long long b = 0; b < blocks(row_lds); ++b) swt_row_fwd_lds_tile<HLEN, 1, NT>(r, b, smem.data());
-        else if (f == 2) for (long long b = 0; b < blocks(row_lds); ++b) swt_row_fwd_lds_tile<HLEN, 2, NT>(r, b, smem.data());
-        else if (f == 4 && !direct) for (long long b = 0; b < blocks(row_lds); ++b) swt_row_fwd_lds_tile<HLEN, 4, NT>(r, b, smem.data());
-        else for (long long b = 0; b < blocks(row_items4); ++b) swt_row_fwd4_tile<HLEN, R, NT>(r, b);
-        SwtSplitArgs c = k;
-        c.in[0] = tmp; c.in[1] = tmp + plane; c.in_bstride = 2 * plane;
-        c.out[0] = a.A; c.out[1] = a.H; c.out[2] = a.V; c.out[3] = a.D; c.out_bstride = a.bstride;
-        if (colstream && run_swt_colstream<HLEN, false>(c)) return;
-        for (long long b = 0; b < blocks(col_items); ++b) swt_col_fwd_tile<HLEN, R, NT>(c, b);
-        return;
-    }
-    SwtSplitArgs c = k;
-    c.in[0] = a.A; c.in[1] = a.H; c.in[2] = a.V; c.in[3] = a.D; c.in_bstride = a.bstride; c.out[0] = tmp; c.out_bstride = 2 * plane;
-    if (!(colstream && run_swt_colstream<HLEN, true>(c)))
-        for (long long b = 0; b < blocks(col_items); ++b) swt_col_inv_tile<HLEN, R, NT>(c, b);
-    SwtSplitArgs r = k;
-    r.in[0] = tmp; r.in_bstride = 2 * plane; r.out[0] = a.out; r.out_bstride = a.bstride;
-    if (f == 1) for (long long b = 0; b < blocks(row_lds); ++b) swt_row_inv_lds_tile<HLEN, 1, 1, NT>(r, b, smem.data());
-    else if (f == 2) for (long long b = 0; b < blocks(row_lds); ++b) swt_row_inv_lds_tile<HLEN, 2, 1, NT>(r, b, smem.data());
-    else if (f == 4 && !direct) for (long long b = 0; b < blocks(row_lds); ++b) swt_row_inv_lds_tile<HLEN, 4, 1, NT>(r, b, smem.data());
-    else for (long long b = 0; b < blocks(row_items4); ++b) swt_row_inv4_tile<HLEN, R, NT>(r, b);
-}
-
-EMU_API int emu_swt2_split(int inverse, float* io, int batch, int Nr, int Nc, int level, const float* lo, const float* hi,
-                           int hlen, float soft_beta, float* A, float* H, float* V, float* D) {
-    Swt2DArgs a;
-    a.in = io; a.out = io; a.A = A; a.H = H; a.V = V; a.D = D;
-    a.Nr = Nr; a.Nc = Nc; a.f = 1 << (level - 1); a.bstride = (long long)Nr * Nc; a.hlen = hlen; a.soft_beta = soft_beta;
-    if ((Nc & 3) || Nc < 16 || a.f >= Nr || a.f >= Nc) return -2;
-    set_bank(a.fb, lo, hi, hlen);
-    std::vector<float> tmp((size_t)2 * Nr * Nc * batch + 16, NAN);
-    switch (hlen) {
-#define X(h) case h: run_swt_split<h>(a, batch, inverse != 0, tmp.data()); return 0;
-        X(4) X(6) X(8) X(10) X(12) X(16) X(20) X(26) X(40)
-#undef X
-    }
-    return -1;
-}
+#include "emu_swt_split.inc"  // (with the column pass as a strip walk)
 
 // ---- one a-trous level as two launches of the any-length stream kernels (swt_stream_kernels.hpp: the fp64 library's long filters);
 // planes as in emu_swt2.  nc = columns per work item (2: pairs where rows are even), R = outputs per work item
@@ -1348,92 +1005,7 @@ EMU_API int emu_dwt2_stream(int inverse, float* io, int batch, int Nr, int Nc, c
     return 0;
 }
 
-// ------------------------------------------------------------------ strip-streaming level kernels for long filters (dwt2_long_kernels.hpp)
-// shape: 0 = <64, 16, 256, KB 2 (inverse 4), M 4, XB 1> (a launch shape), 1 = <32, 8, 128, 2 (4), 2, 2>, 2 = <16, 4, 64, 4, 4, 1>,
-// 3 = <64, 16, 512, 4, 2, 2>
-template <int HLEN, int TXC, int TY, int NT, int KB, int M, int XB>
-static void run_fwd_long(FwdLongArgs a, int batch, int seg) {
-    using G = FwdLongGeom<HLEN, TXC, TY>;
-    a.strips = cdiv(a.Nc2, TXC);
-    a.seg = cdiv(seg < 1 ? a.Nr2 : seg, TY) * TY;
-    a.segs = cdiv(a.Nr2, a.seg);
-    std::vector<float> lds(G::LDS_REALS, NAN);
-    const int chunk = (a.strips * a.segs + 7) / 8;
-    for (int bz = 0; bz < batch; bz++)
-        for (int b = 0; b < 8 * chunk; b++) {
-            int strip, sg;
-            if (!xcd_tile(b, a.strips, a.segs, strip, sg)) continue;
-            std::fill(lds.begin(), lds.end(), NAN);  // a workgroup never reads what another one left
-            dwt2_fwd_long_wg<HLEN, TXC, TY, NT, KB, M, XB>(a, strip, sg, bz, lds.data());
-        }
-}
-
-// Nr, Nc even, Nc % 4 == 0, Nr >= 2 TY of the shape; seg = output rows per segment (rounded up to whole steps; < 1: one segment)
-EMU_API int emu_dwt2_fwd_long(const float* in, int batch, int Nr, int Nc, const float* lo, const float* hi, int hlen, int seg,
-                              int shape, float* A, float* H, float* V, float* D) {
-    if ((hlen & 1) || hlen < kLongMinHlen || hlen > kMaxTaps || (Nr & 1) || (Nc & 3)) return -1;
-    const int ty = shape == 1 ? 8 : (shape == 2 ? 4 : 16);
-    if (Nr < 2 * ty) return -2;
-    FwdLongArgs a;
-    a.in = in; a.A = A; a.H = H; a.V = V; a.D = D;
-    a.Nr = Nr; a.Nc = Nc; a.Nr2 = Nr / 2; a.Nc2 = Nc / 2;
-    a.in_bstride = (long long)Nr * Nc; a.out_bstride = (long long)a.Nr2 * a.Nc2;
-    interleave_bank(a.fb, lo, hi, hlen);
-    switch (hlen) {
-#define X(h) case h:                                                            \
-        if (shape == 0) run_fwd_long<h, 64, 16, 256, 2, 4, 1>(a, batch, seg);    \
-        else if (shape == 1) run_fwd_long<h, 32, 8, 128, 2, 2, 2>(a, batch, seg); \
-        else if (shape == 2) run_fwd_long<h, 16, 4, 64, 4, 4, 1>(a, batch, seg);  \
-        else run_fwd_long<h, 64, 16, 512, 4, 2, 2>(a, batch, seg);               \
-        return 0;
-        X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32) X(34) X(36) X(38) X(40)
-#undef X
-    }
-    return -1;
-}
-
-template <int HLEN, int TXC, int TY, int NT, int KB, int M, int XB>
-static void run_inv_long(InvLongArgs a, int batch, int seg, const float* lo, const float* hi) {
-    using G = InvLongGeom<HLEN, TXC, TY>;
-    a.strips = cdiv(a.Ncc, TXC);
-    a.seg = cdiv(seg < 1 ? a.Nrc : seg, TY) * TY;
-    a.segs = cdiv(a.Nrc, a.seg);
-    long_syn_tables<HLEN>(a, lo, hi);
-    std::vector<float> lds(G::LDS_REALS, NAN);
-    const int chunk = (a.strips * a.segs + 7) / 8;
-    for (int bz = 0; bz < batch; bz++)
-        for (int b = 0; b < 8 * chunk; b++) {
-            int strip, sg;
-            if (!xcd_tile(b, a.strips, a.segs, strip, sg)) continue;
-            std::fill(lds.begin(), lds.end(), NAN);
-            dwt2_inv_long_wg<HLEN, TXC, TY, NT, KB, M, XB>(a, strip, sg, bz, lds.data());
-        }
-}
-
-// Ncc % 4 == 0, Nc == 2 Ncc, Nr == 2 Nrc, Nrc >= TY of the shape; seg = coefficient rows per segment
-EMU_API int emu_dwt2_inv_long(const float* A, const float* H, const float* V, const float* D, int batch, int Nrc, int Ncc,
-                              int Nr, int Nc, const float* lo, const float* hi, int hlen, int seg, int shape, float* out) {
-    if ((hlen & 1) || hlen < kLongMinHlen || hlen > kMaxTaps || (Ncc & 3) || Nc != 2 * Ncc || Nr != 2 * Nrc) return -1;
-    const int ty = shape == 1 ? 8 : (shape == 2 ? 4 : 16);
-    if (Nrc < ty) return -2;
-    InvLongArgs a;
-    a.A = A; a.H = H; a.V = V; a.D = D; a.out = out;
-    a.Nrc = Nrc; a.Ncc = Ncc; a.Nr = Nr; a.Nc = Nc;
-    a.in_bstride = (long long)Nrc * Ncc; a.out_bstride = (long long)Nr * Nc;
-    std::vector<float> plo(kMaxTaps, 0.f), phi(kMaxTaps, 0.f);
-    for (int i = 0; i < hlen; i++) { plo[i] = lo[i]; phi[i] = hi[i]; }
-    switch (hlen) {
-#define X(h) case h:                                                            \
-        if (shape == 0) run_inv_long<h, 64, 16, 256, 4, 4, 1>(a, batch, seg, plo.data(), phi.data());    \
-        else if (shape == 1) run_inv_long<h, 32, 8, 128, 4, 2, 2>(a, batch, seg, plo.data(), phi.data()); \
-        else if (shape == 2) run_inv_long<h, 16, 4, 64, 4, 4, 1>(a, batch, seg, plo.data(), phi.data());  \
-        else run_inv_long<h, 64, 16, 512, 8, 2, 2>(a, batch, seg, plo.data(), phi.data());               \
-        return 0;
-        X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32) X(34) X(36) X(38) X(40)
-#undef X
-    }
-    return -1;
-}
+#include "emu_dwt2_long.inc"
 
 // one row of the lazy-state table (lazy_state.hpp): {refuses after inverse(), what becomes of a pending threshold, of a consumed one};
 // -1 past the last Entry

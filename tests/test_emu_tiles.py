@@ -1051,6 +1051,28 @@ def test_strip_walk_geometry_host_functions():
                 q = xa + 4 * g                     # a group covers columns q .. q + 3 of the periodic row
                 lo, hi = q % Nc, (q + 3) % Nc
                 assert hi == lo + 3 or q + 3 < x0 or q >= x0 + xs, (Nc, x0, xs, pad, g)  # inside the needed window no group wraps
+    _no_loaded_group_leaves_its_row(L.emu_swt_stage_col)
+
+
+def _no_loaded_group_leaves_its_row(stage_col):
+    """stage_col(x0, xs, Nc, g): the source column of group g of a staged row, as the one-launch SWT kernels compute it.  They load
+    NQ = (xs + 6) / 4 groups per row whatever the pad: EVERY one of them lies inside its row -- also those behind the needed
+    window, whose samples the staging discards (behind the last row of the last image lies no plane).  Windows as the kernels'
+    strips make them: x0 = 64 k - c f, xs = 64 + (hlen - 1) f; the launcher declines narrower rows that are not whole groups."""
+    checked = 0
+    for Nc in list(range(150, 420)) + [1001, 1022, 2047]:
+        windows = [(-7, 71), (-19, 103), (Nc - 90, 103), (Nc - 64 - 3, 79), (64 - 38, 142), (-304, 688 if Nc > 700 else 100)]
+        for hlen, f in ((6, 1), (8, 1), (8, 2), (16, 2), (20, 1), (20, 4), (40, 2)):
+            xs = 64 + (hlen - 1) * f
+            windows += [(64 * k - (hlen // 2 - 1) * f, xs) for k in range((Nc + 63) // 64)]
+        for x0, xs in windows:
+            if (xs + 4 > Nc and Nc % 4) or (x0 < 0 and not (x0 > -Nc and x0 + xs > 0)):
+                continue
+            for g in range((xs + 6) // 4):
+                col = stage_col(x0, xs, Nc, g)
+                assert 0 <= col and col + 3 < Nc, (Nc, x0, xs, g, col)
+                checked += 1
+    assert checked > 100000
 
 
 @pytest.mark.parametrize("seg", [0, 32])

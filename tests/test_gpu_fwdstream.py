@@ -48,7 +48,10 @@ def test_fwdstream_levels_vs_oracle(wname):
     # strip; four levels (dilation 8: steps of 16 rows); one step per chain
     # ... and rows that are not whole 16-B groups (the reference takes any width): every residue mod 4
     for si, (shape, levels) in enumerate([((256, 256), 2), ((135, 200), 2), ((97, 36), 1), ((256, 324), 4), ((640, 128), 3), ((33, 520), 1),
-                                          ((130, 1001), 2), ((64, 1022), 1), ((96, 2047), 3)]):
+                                          ((130, 1001), 2), ((64, 1022), 1), ((96, 2047), 3),
+                                          # ... at widths where a 16-B group of the staged row behind the needed window would begin
+                                          # inside the row and end behind it (8 taps: 64 x 133 ... 135; 16 taps, dilation 2: 66 x 161)
+                                          ((64, 133), 1), ((64, 134), 1), ((64, 135), 1), ((66, 161), 2)]):
         if shape[1] % 4 and shape[1] < 64 + (hlen - 1) * (1 << (levels - 1)) + 4:
             continue  # (narrower than one staged window of the deepest level: those levels run on the other kernels)
         x = oracle.hash_input(shape, 9990 + 13 * si + hlen)
@@ -76,6 +79,34 @@ def test_fwdstream_declines_what_it_cannot_take():
             assert np.abs(g - r).max() <= 2e-6 * (1 + w.levels) * max(float(np.abs(r).max()), 255.0), shape
         names = _names(x, "db4", w.levels)
         assert [n == "swt2_fwd_stream" for n in names] == expect, (shape, names)
+
+
+def test_fwdstream_on_a_bound_image_of_exactly_its_size():
+    """pdwt_bind_image on a device allocation of exactly Nr x Nc samples (no arena behind the last row): the widths at which a
+    staged group behind the needed window used to reach past the last row's end; every band against the oracle."""
+    import ctypes as C
+    from pypwt_amd import Wavelets, _lib
+    lib = _lib.load()
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipFree.argtypes = [C.c_void_p]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    for wname, shape, levels in (("db4", (64, 133), 1), ("db4", (64, 134), 1), ("db4", (64, 135), 1), ("sym8", (66, 161), 2)):
+        x = oracle.hash_input(shape, 9940 + shape[1])
+        w = Wavelets(np.zeros(shape, dtype=np.float32), wname, levels, do_swt=1)
+        assert w.levels == levels
+        dev = C.c_void_p()
+        assert hip.hipMalloc(C.byref(dev), x.nbytes) == 0
+        try:
+            assert hip.hipMemcpy(dev, x.ctypes.data, x.nbytes, 1) == 0
+            assert lib.pdwt_bind_image(w._h, dev) == 0 and lib.pdwt_image_ptr(w._h) == dev.value
+            w.forward()
+            got = _flat(w.coeffs)  # (copies to the host: the plan's stream has finished with the image)
+        finally:
+            assert lib.pdwt_bind_image(w._h, None) == 0
+            assert hip.hipFree(dev) == 0
+        for k, (g, r) in enumerate(zip(got, oracle.forward(x, wname, levels, do_swt=1))):
+            assert np.abs(g - r).max() <= 2e-6 * (1 + levels) * max(float(np.abs(r).max()), 255.0), (wname, shape, k)
 
 
 def test_fwdstream_batches_and_custom_banks():

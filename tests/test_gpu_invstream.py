@@ -47,7 +47,9 @@ def test_invstream_levels_vs_oracle(wname):
     hlen = oracle.filters(wname)[0]
     assert 6 <= hlen <= 28 and hlen % 2 == 0, wname
     for si, (shape, levels) in enumerate([((256, 256), 2), ((135, 200), 2), ((97, 36), 1), ((256, 324), 4), ((640, 128), 3), ((33, 520), 1),
-                                          ((130, 1001), 2), ((64, 1022), 1), ((96, 2047), 3)]):
+                                          ((130, 1001), 2), ((64, 1022), 1), ((96, 2047), 3),
+                                          # (widths where a staged group behind the needed window would cross the row end)
+                                          ((64, 133), 1), ((64, 134), 1), ((64, 135), 1), ((66, 161), 2)]):
         if shape[1] % 4 and shape[1] < 64 + (hlen - 1) * (1 << (levels - 1)) + 4:
             continue
         x = oracle.hash_input(shape, 10100 + 13 * si + hlen)
