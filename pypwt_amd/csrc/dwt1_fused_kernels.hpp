@@ -434,7 +434,8 @@ PDWT_DEVICE void dwt1_inv_fused_tile(const Inv1DFusedArgs& a, int bx, int row, f
                     float* dst = na + 8 * m - lom4;
                     *reinterpret_cast<f32x4*>(dst) = r0;
                     *reinterpret_cast<f32x4*>(dst + 4) = r1;
-                } else {      // level 0: [lom, him) = [bx T0, min(.., N0)) is a union of whole 8-sample blocks
+                } else {      // level 0: [lom, him) = [bx T0, min(.., N0)) is a union of whole 8-sample blocks (N0 % 8 == 0: the
+                              // launcher sends K >= 2 levels of rows of 2^(K+1) n samples)
                     *reinterpret_cast<f32x4*>(out + 8 * m) = r0;
                     *reinterpret_cast<f32x4*>(out + 8 * m + 4) = r1;
                 }

@@ -167,7 +167,7 @@ inline void reg1_fwd_blocks(int hlen, int K, int N0, int* nblk, int* nplain) {
 // range-checked store of four values (16 B; fp64: two 16-B halves) -- see RowBuf in dwt2_wave_kernels.hpp
 #ifdef PDWT_CPU_EMU
 PDWT_DEVICE void row_st16(const RowBuf& r, unsigned off, real_t x, real_t y, real_t z, real_t w) {
-    if (off < r.bytes) { real_t* p = reinterpret_cast<real_t*>(r.base + off); p[0] = x; p[1] = y; p[2] = z; p[3] = w; }
+    if (row_in_range(r, off, 4 * (unsigned)sizeof(real_t))) { real_t* p = reinterpret_cast<real_t*>(r.base + off); p[0] = x; p[1] = y; p[2] = z; p[3] = w; }
 }
 #else
 static __device__ __forceinline__ void row_st16(const RowBuf& r, unsigned off, float x, float y, float z, float w) {

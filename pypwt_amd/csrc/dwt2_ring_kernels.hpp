@@ -459,7 +459,7 @@ struct InvRingGeom {
 template <int N>
 PDWT_DEVICE void row_stn(const RowBuf& r, unsigned off, const real_t* v) {
 #ifdef PDWT_CPU_EMU
-    if (off < r.bytes) {
+    if (row_in_range(r, off, N * (unsigned)sizeof(real_t))) {
         real_t* p = reinterpret_cast<real_t*>(r.base + off);
         for (int i = 0; i < N; ++i) p[i] = v[i];
     }

@@ -573,11 +573,17 @@ struct RowBuf {
     unsigned bytes;
 };
 PDWT_DEVICE RowBuf row_buf(real_t* row, unsigned row_bytes) { return RowBuf{(char*)row, row_bytes}; }
+// A store that lies partly in range is one no kernel should issue (what the hardware does with it is nothing to rest on): it aborts.
+PDWT_DEVICE bool row_in_range(const RowBuf& r, unsigned off, unsigned size) {
+    if (off >= r.bytes) return false;
+    if (size > r.bytes - off) abort();
+    return true;
+}
 PDWT_DEVICE void row_st8(const RowBuf& r, unsigned off, real_t x, real_t y) {
-    if (off < r.bytes) { real_t* p = reinterpret_cast<real_t*>(r.base + off); p[0] = x; p[1] = y; }
+    if (row_in_range(r, off, 2 * (unsigned)sizeof(real_t))) { real_t* p = reinterpret_cast<real_t*>(r.base + off); p[0] = x; p[1] = y; }
 }
 PDWT_DEVICE void row_st4(const RowBuf& r, unsigned off, real_t x) {
-    if (off < r.bytes) *reinterpret_cast<real_t*>(r.base + off) = x;
+    if (row_in_range(r, off, (unsigned)sizeof(real_t))) *reinterpret_cast<real_t*>(r.base + off) = x;
 }
 #else
 struct RowBuf {

@@ -137,6 +137,10 @@ hipError_t launch_dwt1_fwd_fused(const float* in, float* const* det, float* app,
         const hipError_t e = launch_rows_tail(in, det, app, rows, N0, K, hlen, false, fb, s);
         if (e != hipErrorNotSupported) return e;
     }
+    // The pyramid kernels below are written for two levels and more: with one, the forward's staging origin is not 4-aligned and the
+    // inverse's 8-sample output blocks end behind a row of 8 n + 4 samples (found under the sanitizers, tests/test_emu_sanitized_more.py).
+    // A single level reaches here only if the several-rows kernels declined it: the planner then runs the level kernels.
+    if (K < 2) return hipErrorNotSupported;
     // TF = 64 final-level outputs per workgroup at K = 6 (TF = 128 measured 25 % slower on 2^24 sym8 L6: 55 KB of LDS leaves 2
     // workgroups per CU), i.e. a segment of 64 * 2^K = 4096 input samples.  With FEWER levels the segment of TF = 64 shrinks
     // to 512 samples at K = 3 -- two per thread, 32768 workgroups for 4096 rows of 4096: the forward took 55-65 us where the
@@ -184,6 +188,7 @@ hipError_t launch_dwt1_inv_fused(const float* app, const float* const* det, floa
         const hipError_t e = launch_rows_tail(app, const_cast<float* const*>(det), out, rows, N0, K, hlen, true, fb, s);
         if (e != hipErrorNotSupported) return e;
     }
+    if (K < 2) return hipErrorNotSupported;  // (as in the forward launcher: the pyramid kernels take two levels and more)
     if (short_rows(N0) && hlen <= 20) {
         switch (hlen) {
 #define X(h) case h: if constexpr (h <= 20) return run_inv_rows<h>(a, s); break;

@@ -24,13 +24,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from emu_san_util import IN, OUT, SAN, compile_programs
+from emu_san_util import nan as _nan
+from emu_san_util import plane as _plane
+from emu_san_util import run as _run
 from emu_util import EMU_DIR, P, lib
 from oracle import oracle
 
-SRC = os.path.join(EMU_DIR, "emu_san.cpp")
-SAN = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-DPDWT_CPU_EMU", "-DEMU_SLACK=0",
-       "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-static-libasan",
-       "-static-libubsan"]
 # family -> what selects it and the filter lengths / dilations its program instantiates (the cases below use no other)
 FAMILIES = {
     "fwdstream": ["-DEMU_SAN_FWDSTREAM", "-DEMU_FWDSTREAM_HLENS(X)=X(6) X(8) X(20)", "-DEMU_FWDSTREAM_DILATIONS(Y,h)=Y(h,1) Y(h,2) Y(h,4)"],
@@ -40,73 +40,14 @@ FAMILIES = {
     "split": ["-DEMU_SAN_SPLIT", "-DEMU_SPLIT_HLENS(X)=X(10) X(20)"],
     "long": ["-DEMU_SAN_LONG", "-DEMU_LONG_HLENS(X)=X(10) X(20) X(40)"],
 }
-IN, OUT = 0, 1
 
 
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
-    """Every family's program, compiled side by side on first use; family -> a function returning its path."""
-    d = tmp_path_factory.mktemp("emu_san")
-    procs = {f: subprocess.Popen(SAN + flags + ["-o", str(d / f), SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-             for f, flags in FAMILIES.items()}
-
-    logs = {}
-
-    def get(family):
-        if family not in logs:
-            logs[family] = procs[family].communicate()[0]
-        assert procs[family].returncode == 0, logs[family][-3000:]
-        return str(d / family)
+    """Every family's program, compiled side by side (emu_san_util.compile_programs); family -> a function returning its path."""
+    get, finish = compile_programs(tmp_path_factory.mktemp("emu_san"), FAMILIES)
     yield get
-    for p in procs.values():
-        p.wait()
-    _inputs.clear()
-
-
-def _record(f, ints, flts, bufs):
-    """One record of emu_san.cpp's input; bufs: (array or None, IN / OUT)."""
-    f.write(np.array([len(ints)] + list(ints), dtype=np.int64).tobytes())
-    f.write(np.array([len(flts)], dtype=np.int64).tobytes() + np.array(flts, dtype=np.float32).tobytes())
-    f.write(np.array([len(bufs)], dtype=np.int64).tobytes())
-    for a, kind in bufs:
-        f.write(np.array([-1 if a is None else a.size, kind], dtype=np.int64).tobytes())
-        if a is not None and kind == IN:
-            assert a.dtype == np.float32 and a.flags.c_contiguous
-            f.write(a.tobytes())
-
-
-def _run(exe, tmp_path, cases):
-    """cases: (ints, flts, bufs) with the OUT arrays already filled by the unsanitised library.  Runs the program once."""
-    data, res = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")
-    with open(data, "wb") as f:
-        for ints, flts, bufs in cases:
-            _record(f, ints, flts, bufs)
-    env = {k: v for k, v in os.environ.items() if k not in ("EMU_SPLIT_COLSTREAM", "EMU_COLSTREAM_SEG", "EMU_SPLIT_DIRECT")}
-    r = subprocess.run([exe, data, res], capture_output=True, text=True, timeout=900,
-                       env=dict(env, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1"))
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    assert int(r.stdout.split()[-1]) == len(cases)
-    want = np.concatenate([a.ravel() for _, _, bufs in cases for a, kind in bufs if kind == OUT and a is not None])
-    assert not np.isnan(want).any()  # the library wrote every output element
-    got = np.fromfile(res, dtype=np.float32)
-    assert got.shape == want.shape
-    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
-
-
-_inputs = {}
-
-
-def _plane(shape, seed, signed=False):
-    """oracle.hash_input, as in tests/test_emu_tiles.py (coefficients: in [-1, 1)); computed once per (shape, seed)."""
-    key = (shape, seed, signed)
-    if key not in _inputs:
-        x = oracle.hash_input(shape, seed, 2.0) - 1.0 if signed else oracle.hash_input(shape, seed)
-        _inputs[key] = np.ascontiguousarray(x, dtype=np.float32)
-    return _inputs[key]
-
-
-def _nan(shape):
-    return np.full(shape, np.nan, dtype=np.float32)
+    finish()
 
 
 def _widths(hlen, f):
