@@ -336,7 +336,7 @@ const char* pdwt_comm_last_error(void);
  *   - pointers from pdwt_volume_image_ptr / pdwt_volume_coeff_ptr are borrowed and valid while the volume lives.
  * pdwt_volume_layout is a pure host function (no device needed): the clamped level count into *nlevels, (depth, rows, cols) of
  * num 0 .. capacity - 1 into dims[3 num + {0,1,2}]; returns the number of bands 1 + 7 L, or a negative status.
- * Out of scope: 3D SWT through this constructor (pdwt_volume_create_swt below is the stationary transform), non-separable volumes, custom filter banks, cycle spinning, clone (add_wavelet, shrink, the group
+ * Out of scope: 3D SWT through this constructor (pdwt_volume_create_swt below is the stationary transform), non-separable volumes, custom filter banks, clone (cycle spinning is at the end of this header; add_wavelet, shrink, the group
  * threshold and proj_linf are further down), the compiled Cython class, ShardedBatch / TiledWavelets for volumes, a fused kernel that does all three axes in
  * one read, a fused stats + threshold sweep. */
 typedef struct pdwt_volume* pdwt_volume_handle;
@@ -456,6 +456,38 @@ int pdwt_volume_shrink(pdwt_volume_handle h, pdwt_real beta, int do_thresh_appco
 int pdwt_volume_add_wavelet(pdwt_volume_handle dst, pdwt_volume_handle src, pdwt_real alpha);
 int pdwt_volume_group_norm(pdwt_volume_handle h, int do_thresh_appcoeffs, double* out);
 int pdwt_volume_group_norm_async(pdwt_volume_handle h, int do_thresh_appcoeffs, double* d_out, double** d_slot);
+
+/* Circular shifts and cycle spinning of a volume (the reference's pdwt_circshift / do_cycle_spinning, wt.cu:242-246, 303 and
+ * common.cu:202-211, 378-396, exist for 2D plans only).
+ *   - pdwt_volume_circshift: image <- numpy.roll(image, (sz, sr, sc)), out[z][r][c] = in[z - sz][r - sr][c - sc] with every index
+ *     modulo its size: pdwt_circshift's sense on rows and columns, the same on depth.  Shifts may be negative or beyond the size.
+ *     In place as the caller sees it (pdwt_volume_image_ptr does not change), on the volume's stream, decimated and stationary
+ *     volumes alike; the scratch is the level-1 stack.  The image must be current -- set, or written by pdwt_volume_inverse --:
+ *     after pdwt_volume_forward it returns PDWT_ERR_STATE and does nothing.  The state afterwards is that after set_image;
+ *   - pdwt_volume_set_cycle_spinning(on, seed): every pdwt_volume_forward first shifts the image by a pseudo-random (sz, sr, sc),
+ *     drawn on the host by a generator that depends on `seed` alone, and the matching pdwt_volume_inverse shifts the result back
+ *     (Coifman and Donoho's cycle spinning, one shift per iteration of an iterative reconstruction).  Off by default: a volume
+ *     that never turned it on behaves bit for bit as before.  pdwt_volume_current_shift: what the image is shifted by in all since
+ *     it was set -- the last draw, or the sum of the draws of forwards in a row --, (0, 0, 0) after an inverse, after set_image and
+ *     on a volume without cycle spinning.  Stationary volumes: PDWT_ERR_UNSUPPORTED (as pdwt_create refuses cycle spinning with SWT);
+ *   - pdwt_volume_cycle_spin_async: the averaged estimator  image <- 1/K sum_s S_-s T^-1 theta T S_s image  over the K = nshifts
+ *     shifts (sz, sr, sc) of `shifts` (host memory, read before the call returns), everything enqueued on the volume's stream.
+ *     theta is, with method = PDWT_SPIN_GLOBAL, the soft (op 0) or hard (op 1) threshold with the global beta, exactly
+ *     pdwt_volume_soft_threshold / _hard_threshold(beta, do_thresh_appcoeffs, normalize); with method = PDWT_DENOISE_BAYES or
+ *     PDWT_DENOISE_VISU it is pdwt_volume_denoise_async(method, op, sigma, skip_zeros): with sigma NULL every shift estimates its
+ *     own noise level.  The running mean has the volume's precision; the state afterwards is that after pdwt_volume_inverse.  Two
+ *     extra volumes (pdwt_volume_spin_footprint tells their bytes; a pure host function, real_bytes 4, 8 or 0 = this library's) are
+ *     allocated by the first call and freed with the volume; a failed allocation returns PDWT_ERR_NOMEM, leaves nothing behind
+ *     and the volume usable.  Refused with nothing launched: nshifts < 1, a null `shifts`, an unknown op or method (PDWT_ERR_ARG);
+ *     an image that is not current, or a volume with cycle spinning on -- the two would compose -- (PDWT_ERR_STATE); a stationary
+ *     volume (PDWT_ERR_UNSUPPORTED). */
+#define PDWT_SPIN_GLOBAL (-1)
+int pdwt_volume_circshift(pdwt_volume_handle h, int sz, int sr, int sc);
+int pdwt_volume_set_cycle_spinning(pdwt_volume_handle h, int on, unsigned long long seed);
+int pdwt_volume_current_shift(pdwt_volume_handle h, int shift[3]);
+int pdwt_volume_cycle_spin_async(pdwt_volume_handle h, int nshifts, const int* shifts, int op, double beta, int do_thresh_appcoeffs,
+                                 int normalize, int method, const double* sigma, int skip_zeros);
+int pdwt_volume_spin_footprint(int Nz, int Nr, int Nc, size_t real_bytes, size_t* extra_bytes);
 
 #ifdef __cplusplus
 }

@@ -165,6 +165,12 @@ def signatures(real=C.c_float):
         "pdwt_volume_add_wavelet": (C.c_int, [handle_t, handle_t, real]),
         "pdwt_volume_group_norm": (C.c_int, [handle_t, C.c_int, C.POINTER(C.c_double)]),
         "pdwt_volume_group_norm_async": (C.c_int, [handle_t, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+        "pdwt_volume_circshift": (C.c_int, [handle_t, C.c_int, C.c_int, C.c_int]),
+        "pdwt_volume_set_cycle_spinning": (C.c_int, [handle_t, C.c_int, C.c_ulonglong]),
+        "pdwt_volume_current_shift": (C.c_int, [handle_t, C.POINTER(C.c_int)]),
+        "pdwt_volume_cycle_spin_async": (C.c_int, [handle_t, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_double), C.c_int]),
+        "pdwt_volume_spin_footprint": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
         "pdwt_volume_set_filters": (C.c_int, [handle_t, C.c_int, realp, realp, realp, realp]),
         "pdwt_volume_set_depth_segments": (C.c_int, [handle_t, C.c_int, C.c_int, C.c_int]),
         "pdwt_volume_depth_width": (C.c_int, [handle_t, C.c_int, C.c_int]),

@@ -254,6 +254,10 @@ struct VolGroupTable;
 struct VolGroupBetas;
 hipError_t launch_vol_group_soft(const VolGroupTable& t, const VolGroupBetas& betas, int with_app, hipStream_t s);
 hipError_t launch_vol_group_norm(const VolGroupTable& t, int with_app, double* partial, double* out, hipStream_t s);
+// circular shifts of a volume [Nz][Nr][Nc] (volume_shift_kernels.hpp), out of place: numpy.roll(in, (sz, sr, sc)) for shifts of any
+// sign and size, and the weighted shift BACK into a running mean, acc = (first ? 0 : acc) + w roll(rec, (-sz, -sr, -sc))
+hipError_t launch_vol_circshift(const real_t* in, real_t* out, int Nz, int Nr, int Nc, int sz, int sr, int sc, hipStream_t s);
+hipError_t launch_vol_unshift_acc(const real_t* rec, real_t* acc, int Nz, int Nr, int Nc, int sz, int sr, int sc, real_t w, int first, hipStream_t s);
 hipError_t launch_circshift(const real_t* in, real_t* out, int batch, int Nr, int Nc, int sr, int sc, hipStream_t s);
 hipError_t launch_copy(const real_t* src, real_t* dst, long long n, hipStream_t s);  // 16-B grid-stride copy (n % 4 == 0)
 hipError_t launch_fill_hash(real_t* x, long long n, uint32_t seed, real_t scale, long long index_offset,

@@ -6,6 +6,7 @@
 #include "select_kernels.hpp"
 #undef PDWT_INLINE_HELPERS_ONLY
 #include "volume_ops_kernels.hpp"
+#include "volume_shift_kernels.hpp"
 
 namespace pdwt {
 
@@ -71,6 +72,29 @@ hipError_t launch_vol_group_norm(const VolGroupTable& t, int with_app, double* p
     if (blocks < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(vol_group_norm_kernel, dim3(blocks), dim3(kVolGroupThreads), 0, s, t, with_app ? 1 : 0, partial);
     hipLaunchKernelGGL(vol_group_norm_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, out);
+    return hipGetLastError();
+}
+
+// out = circshift(in, sz, sr, sc) on [Nz][Nr][Nc], the shifts of any sign and size; in and out must not overlap
+hipError_t launch_vol_circshift(const real_t* in, real_t* out, int Nz, int Nr, int Nc, int sz, int sr, int sc, hipStream_t s) {
+    if (Nz < 1 || Nr < 1 || Nc < 1 || !in || !out || in == out) return hipErrorInvalidValue;
+    const VolShiftGeom g = vol_shift_geom_of(Nz, Nr, Nc, sz, sr, sc, false, in, out);
+    const dim3 grid(vol_shift_grid(g)), block(kVolShiftThreads);
+    if (g.mode == 2) hipLaunchKernelGGL(vol_circshift_kernel<2>, grid, block, 0, s, in, out, g);
+    else if (g.mode == 1) hipLaunchKernelGGL(vol_circshift_kernel<1>, grid, block, 0, s, in, out, g);
+    else hipLaunchKernelGGL(vol_circshift_kernel<0>, grid, block, 0, s, in, out, g);
+    return hipGetLastError();
+}
+
+// acc = (first ? 0 : acc) + w circshift(rec, -sz, -sr, -sc): the shift (sz, sr, sc) that was applied is undone
+hipError_t launch_vol_unshift_acc(const real_t* rec, real_t* acc, int Nz, int Nr, int Nc, int sz, int sr, int sc, real_t w, int first, hipStream_t s) {
+    if (Nz < 1 || Nr < 1 || Nc < 1 || !rec || !acc || rec == acc) return hipErrorInvalidValue;
+    const VolShiftGeom g = vol_shift_geom_of(Nz, Nr, Nc, sz, sr, sc, true, rec, acc);
+    const dim3 grid(vol_shift_grid(g)), block(kVolShiftThreads);
+    const int f = first ? 1 : 0;
+    if (g.mode == 2) hipLaunchKernelGGL(vol_unshift_acc_kernel<2>, grid, block, 0, s, rec, acc, g, w, f);
+    else if (g.mode == 1) hipLaunchKernelGGL(vol_unshift_acc_kernel<1>, grid, block, 0, s, rec, acc, g, w, f);
+    else hipLaunchKernelGGL(vol_unshift_acc_kernel<0>, grid, block, 0, s, rec, acc, g, w, f);
     return hipGetLastError();
 }
 

@@ -384,6 +384,57 @@ SwtLayout swt_layout(int Nz, int Nr, int Nc, int L, size_t real_bytes) {
     return y;
 }
 
+
+// ---------------------------------------------------------------- circular shifts and cycle spinning (volume_shift_kernels.hpp)
+
+// the image is what the caller last gave or the last inverse wrote; after a forward it is the transform's input and the level-1
+// stack holds live data
+bool image_current(const pdwt_volume* v) { return v->state == PDWT_INIT || v->state == PDWT_INVERSE; }
+
+// image <- circshift(image, sz, sr, sc) through the level-1 stack: shifted into it, copied back, so that the image stays where it is
+int shift_image(pdwt_volume* v, int sz, int sr, int sc) {
+    if (!vol_shift_reduce(sz, v->Nz) && !vol_shift_reduce(sr, v->Nr) && !vol_shift_reduce(sc, v->Nc)) return PDWT_OK;
+    real_t* tmp = v->shift_scratch();
+    HIP_TRY(launch_vol_circshift(v->image, tmp, v->Nz, v->Nr, v->Nc, sz, sr, sc, v->stream));
+    return v->copy(v->image, tmp, (long long)v->Nz * v->Nr * v->Nc, 0);
+}
+
+// splitmix64: the draws of a cycle-spinning volume depend on its seed alone
+unsigned long long spin_draw(pdwt_volume* v) {
+    unsigned long long z = (v->rng += 0x9E3779B97F4A7C15ULL);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+size_t spin_volume_bytes(int Nz, int Nr, int Nc, size_t real_bytes) { return align256((size_t)Nz * Nr * Nc * real_bytes); }
+
+// the kept source and the running mean of cycle_spin: one block, or nothing
+int ensure_spin(pdwt_volume* v) {
+    if (v->spin_block) return PDWT_OK;
+    const size_t vol = spin_volume_bytes(v->Nz, v->Nr, v->Nc, sizeof(real_t));
+    const hipError_t e = hipMalloc(&v->spin_block, 2 * vol);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        v->spin_block = nullptr;
+        return VFAIL(PDWT_ERR_NOMEM, "cycle_spin: hipMalloc of %zu bytes failed: %s", 2 * vol, hipGetErrorString(e));
+    }
+    v->spin_src = static_cast<real_t*>(v->spin_block);
+    v->spin_acc = reinterpret_cast<real_t*>(static_cast<char*>(v->spin_block) + vol);
+    return PDWT_OK;
+}
+
+// the sweep of pdwt_volume_denoise_async on current coefficients: the noise level is in its slot already, or is estimated
+int denoise_sweep(VolumeDwt* v, int method, int op, bool estimate, int skip_zeros) {
+    VolumeWs* w = v->ops;
+    if (estimate) PDWT_TRY(estimate_sigma_impl(v, skip_zeros, nullptr));
+    if (method == PDWT_DENOISE_BAYES) PDWT_TRY(band_stats_impl(v, nullptr));
+    const double visu = sqrt(2.0 * log((double)v->Nz * (double)v->Nr * (double)v->Nc));
+    HIP_TRY(launch_vol_table(w->levels, w->stats, w->sigma, method, visu, w->table, v->stream));
+    HIP_TRY(launch_vol_expand(w->levels, w->table, v->stream));
+    return sweep_levels(v, op);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- the common part
@@ -399,6 +450,7 @@ VolumeDwt::~VolumeDwt() {
     if (!plans.empty()) (void)hipStreamSynchronize(stream);
     if (ops) free_ops(ops);
     if (group_ws) (void)hipFree(group_ws);
+    if (spin_block) (void)hipFree(spin_block);
     for (size_t i = plans.size(); i-- > 0;) pdwt_destroy(plans[i]);  // plans[0] may own the stream: last
     if (image) (void)hipFree(image);
 }
@@ -504,6 +556,7 @@ VolumeSwt::~VolumeSwt() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (block) (void)hipFree(block);
     if (group_ws) (void)hipFree(group_ws);
+    if (spin_block) (void)hipFree(spin_block);
     if (h_table) (void)hipHostFree(h_table);
     if (staged) (void)hipEventDestroy(staged);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
@@ -832,7 +885,15 @@ int pdwt_volume_destroy(pdwt_volume_handle v) {
 int pdwt_volume_forward(pdwt_volume_handle v) {
     if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
     DeviceGuard guard(v->device);
-    const int rc = v->forward_levels();
+    int rc = PDWT_OK;
+    if (v->do_cycle_spinning) {  // wt.cu:242-246, on three axes (plan.cpp: pdwt_forward)
+        const int n[3] = {v->Nz, v->Nr, v->Nc};
+        int d[3];
+        for (int a = 0; a < 3; a++) d[a] = (int)(spin_draw(v) % (unsigned long long)n[a]);
+        rc = shift_image(v, d[0], d[1], d[2]);
+        for (int a = 0; a < 3 && rc == PDWT_OK; a++) v->shift[a] = vol_shift_reduce((long long)v->shift[a] + d[a], n[a]);
+    }
+    if (rc == PDWT_OK) rc = v->forward_levels();
     v->state = rc == PDWT_OK ? PDWT_FORWARD : PDWT_FORWARD_ERROR;
     return rc;
 }
@@ -844,7 +905,11 @@ int pdwt_volume_inverse(pdwt_volume_handle v) {
     if (v->state == PDWT_FORWARD_ERROR || v->state == PDWT_THRESHOLD_ERROR || v->state == PDWT_CREATION_ERROR)
         return VFAIL(PDWT_ERR_STATE, "inverse transform not computed, as there was an error in a previous stage");
     DeviceGuard guard(v->device);
-    const int rc = v->inverse_levels();
+    int rc = v->inverse_levels();
+    if (rc == PDWT_OK && v->do_cycle_spinning) {  // wt.cu:303
+        rc = shift_image(v, -v->shift[0], -v->shift[1], -v->shift[2]);
+        if (rc == PDWT_OK) v->shift[0] = v->shift[1] = v->shift[2] = 0;
+    }
     v->state = rc == PDWT_OK ? PDWT_INVERSE : PDWT_INVERSE_ERROR;
     return rc;
 }
@@ -873,6 +938,7 @@ int pdwt_volume_set_image(pdwt_volume_handle v, const pdwt_real* src, int mem_is
     DeviceGuard guard(v->device);
     PDWT_TRY(copy_in(v, v->image, src, (long long)v->Nz * v->Nr * v->Nc, mem_is_on_device));
     v->state = PDWT_INIT;
+    v->shift[0] = v->shift[1] = v->shift[2] = 0;  // (a cycle-spinning volume: the new image is not shifted)
     return PDWT_OK;
 }
 
@@ -1060,14 +1126,8 @@ int pdwt_volume_denoise_async(pdwt_volume_handle h, int method, int op, const do
     if (!sigma) PDWT_TRY(noise_check(v, "denoise"));
     DeviceGuard guard(v->device);
     PDWT_TRY(enter_ops(v, "denoise", true));
-    VolumeWs* w = v->ops;
-    if (sigma) PDWT_TRY(stage_upload(v, w->sigma, sigma, sizeof(double)));
-    else PDWT_TRY(estimate_sigma_impl(v, skip_zeros, nullptr));
-    if (method == PDWT_DENOISE_BAYES) PDWT_TRY(band_stats_impl(v, nullptr));
-    const double visu = sqrt(2.0 * log((double)v->Nz * (double)v->Nr * (double)v->Nc));
-    HIP_TRY(launch_vol_table(w->levels, w->stats, w->sigma, method, visu, w->table, v->stream));
-    HIP_TRY(launch_vol_expand(w->levels, w->table, v->stream));
-    return sweep_levels(v, op);
+    if (sigma) PDWT_TRY(stage_upload(v, v->ops->sigma, sigma, sizeof(double)));
+    return denoise_sweep(v, method, op, !sigma, skip_zeros);
 }
 
 int pdwt_volume_adaptive_slots(pdwt_volume_handle h, double** d_stats, double** d_sigma, pdwt_real** d_table) {
@@ -1110,6 +1170,91 @@ int pdwt_volume_sparsify_slots(pdwt_volume_handle h, pdwt_real** d_threshold, un
     if (d_threshold) *d_threshold = v->ops->sp_threshold;
     if (d_kept) *d_kept = v->ops->sp_kept;
     return PDWT_OK;
+}
+
+// ---------------------------------------------------------------- circular shifts and cycle spinning
+int pdwt_volume_circshift(pdwt_volume_handle v, int sz, int sr, int sc) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (!image_current(v)) return VFAIL(PDWT_ERR_STATE, "circshift: the image is not current (forward() has been run; call inverse() or set_image())");
+    DeviceGuard guard(v->device);
+    PDWT_TRY(shift_image(v, sz, sr, sc));
+    v->state = PDWT_INIT;
+    return PDWT_OK;
+}
+
+int pdwt_volume_set_cycle_spinning(pdwt_volume_handle v, int on, unsigned long long seed) {
+    if (!v) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (on && v->do_swt)  // as pdwt_create refuses the combination for a 2D plan
+        return VFAIL(PDWT_ERR_UNSUPPORTED, "cycle spinning is not built for stationary volumes (do_swt): the transform is translation invariant already");
+    if (!on && v->do_cycle_spinning && (v->shift[0] || v->shift[1] || v->shift[2]))
+        return VFAIL(PDWT_ERR_STATE, "set_cycle_spinning: the image is still shifted; run inverse() or set_image() first");
+    v->do_cycle_spinning = on ? 1 : 0;
+    v->rng = seed;
+    return PDWT_OK;
+}
+
+int pdwt_volume_current_shift(pdwt_volume_handle v, int shift[3]) {
+    if (!v || !shift) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_current_shift: null argument");
+    for (int a = 0; a < 3; a++) shift[a] = v->shift[a];
+    return PDWT_OK;
+}
+
+int pdwt_volume_spin_footprint(int Nz, int Nr, int Nc, size_t real_bytes, size_t* extra_bytes) {
+    if (Nz < 1 || Nr < 1 || Nc < 1 || !extra_bytes) return VFAIL(PDWT_ERR_ARG, "pdwt_volume_spin_footprint: bad arguments");
+    if (real_bytes != 0 && real_bytes != 4 && real_bytes != 8)
+        return VFAIL(PDWT_ERR_ARG, "pdwt_volume_spin_footprint: real_bytes must be 4, 8 or 0 (this library's), got %zu", real_bytes);
+    *extra_bytes = 2 * spin_volume_bytes(Nz, Nr, Nc, real_bytes ? real_bytes : sizeof(real_t));
+    return PDWT_OK;
+}
+
+int pdwt_volume_cycle_spin_async(pdwt_volume_handle h, int nshifts, const int* shifts, int op, double beta, int do_app, int normalize,
+                                 int method, const double* sigma, int skip_zeros) {
+    const char* what = "cycle_spin";
+    VolumeDwt* v = nullptr;
+    if (!h) return VFAIL(PDWT_ERR_ARG, "null volume handle");
+    if (h->do_swt)
+        return VFAIL(PDWT_ERR_UNSUPPORTED, "%s: not built for stationary volumes (do_swt): the transform is translation invariant already", what);
+    v = static_cast<VolumeDwt*>(h);
+    if (nshifts < 1 || !shifts) return VFAIL(PDWT_ERR_ARG, "%s: at least one shift is needed", what);
+    if (op != EW_SOFT && op != EW_HARD) return VFAIL(PDWT_ERR_ARG, "%s: op must be 0 (soft) or 1 (hard)", what);
+    const bool adaptive = method != PDWT_SPIN_GLOBAL;
+    if (adaptive && method != PDWT_DENOISE_BAYES && method != PDWT_DENOISE_VISU) return VFAIL(PDWT_ERR_ARG, "%s: unknown method %d", what, method);
+    if (!image_current(v)) return VFAIL(PDWT_ERR_STATE, "%s: the image is not current (forward() has been run; call inverse() or set_image())", what);
+    if (v->do_cycle_spinning) return VFAIL(PDWT_ERR_STATE, "%s: the volume draws a shift of its own per forward (set_cycle_spinning); the two would compose", what);
+    if (adaptive && !sigma) PDWT_TRY(noise_check(v, what));
+    DeviceGuard guard(v->device);
+    PDWT_TRY(ensure_spin(v));
+    if (adaptive) {
+        PDWT_TRY(ensure_ops(v));
+        if (sigma) PDWT_TRY(stage_upload(v, v->ops->sigma, sigma, sizeof(double)));  // once: nothing below writes the slot
+    }
+    std::vector<real_t> level_betas;
+    const real_t app = level_thresholds((real_t)beta, v->nlevels, do_app, normalize, &level_betas);
+    const long long n = (long long)v->Nz * v->Nr * v->Nc;
+    const real_t w = (real_t)(1.0 / nshifts);
+    int rc = v->copy(v->spin_src, v->image, n, 0);
+    for (int s = 0; s < nshifts && rc == PDWT_OK; s++) {
+        const int* d = shifts + 3 * s;
+        hipError_t e = launch_vol_circshift(v->spin_src, v->image, v->Nz, v->Nr, v->Nc, d[0], d[1], d[2], v->stream);
+        if (e != hipSuccess) rc = VFAIL(PDWT_ERR_HIP, "%s: shift %d failed: %s", what, s, hipGetErrorString(e));
+        if (rc == PDWT_OK) rc = v->forward_levels();
+        if (rc == PDWT_OK) {
+            if (adaptive) {
+                rc = mark_current(v);
+                if (rc == PDWT_OK) rc = denoise_sweep(v, method, op, !sigma, skip_zeros);
+            } else {
+                rc = v->threshold(op, level_betas.data(), app, what);
+            }
+        }
+        if (rc == PDWT_OK) rc = v->inverse_levels();
+        if (rc == PDWT_OK) {
+            e = launch_vol_unshift_acc(v->image, v->spin_acc, v->Nz, v->Nr, v->Nc, d[0], d[1], d[2], w, s == 0, v->stream);
+            if (e != hipSuccess) rc = VFAIL(PDWT_ERR_HIP, "%s: accumulation of shift %d failed: %s", what, s, hipGetErrorString(e));
+        }
+    }
+    if (rc == PDWT_OK) rc = v->copy(v->image, v->spin_acc, n, 0);
+    v->state = rc == PDWT_OK ? PDWT_INVERSE : PDWT_INVERSE_ERROR;
+    return rc;
 }
 
 int pdwt_volume_read(pdwt_volume_handle v, void* dst, const void* d_src, long long bytes) {

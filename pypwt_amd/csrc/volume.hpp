@@ -14,6 +14,7 @@
 // the range and level tables of the volume's operators and their index math; the kernels belong to launch_volume_ops.hip
 #define PDWT_INLINE_HELPERS_ONLY
 #include "volume_ops_kernels.hpp"
+#include "volume_shift_kernels.hpp"
 #undef PDWT_INLINE_HELPERS_ONLY
 
 namespace pdwt {
@@ -64,6 +65,14 @@ struct pdwt_volume {
     // norm's workspace -- [0] the result slot, then one partial sum per piece --, allocated by the first call that needs it
     pdwt::VolGroupTable groups{};
     double* group_ws = nullptr;
+    // cycle spinning (pdwt_volume_set_cycle_spinning): every forward shifts the image by a fresh draw of `rng`; `shift` is what the
+    // image is shifted by IN ALL since the caller gave it (the draws of forwards in a row add up), undone by the next inverse
+    int do_cycle_spinning = 0;
+    int shift[3] = {0, 0, 0};
+    unsigned long long rng = 0;
+    // pdwt_volume_cycle_spin_async: one block of two volumes -- the kept source and the running mean --, allocated by its first call
+    void* spin_block = nullptr;
+    real_t *spin_src = nullptr, *spin_acc = nullptr;
 
     explicit pdwt_volume(int swt) : do_swt(swt) {}
     pdwt_volume(const pdwt_volume&) = delete;
@@ -75,6 +84,8 @@ struct pdwt_volume {
     virtual int inverse_levels() = 0;
     virtual real_t* sub_ptr(const pdwt::SubBand& s) const = 0;
     virtual real_t* approx_ptr(int level) const = 0;  // A_l; the image for l = 0
+    // at least one volume of scratch that is dead while the image is current: the level-1 stack
+    virtual real_t* shift_scratch() const = 0;
     // host <-> device copies on the volume's stream (kind 0 d2d, 1 h2d, 2 d2h; the host kinds return when the copy is done)
     virtual int copy(void* dst, const void* src, long long count, int kind) = 0;
     // the global soft / hard threshold: level_betas[l - 1] on the details of level l, app_beta_or_nan on A_L (NaN: left alone)
@@ -128,6 +139,7 @@ struct VolumeDwt final : pdwt_volume {
     int walk_steps(int level, bool inverse) const override;
     int set_filters(int hlen, const real_t* dec_lo, const real_t* dec_hi, const real_t* rec_lo, const real_t* rec_hi) override;
     real_t* stack_ptr(int level) const;  // what level l's depth pass writes: its plan's image slot
+    real_t* shift_scratch() const override { return stack_ptr(1); }
 };
 
 // The STATIONARY volume: no level plans, ONE device block.  Level l = the a-trous depth pass (swt3_axis_kernels.hpp)
@@ -161,6 +173,7 @@ struct VolumeSwt final : pdwt_volume {
     int inverse_levels() override;
     real_t* sub_ptr(const SubBand& s) const override;
     real_t* approx_ptr(int level) const override;
+    real_t* shift_scratch() const override { return stack; }
     int copy(void* dst, const void* src, long long count, int kind) override;
     int threshold(int op, const real_t* level_betas, real_t app_beta_or_nan, const char* what) override;
     int norms(double out[2]) override;

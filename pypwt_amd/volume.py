@@ -10,7 +10,9 @@ rest of the library (pywt's "periodization").  ctypes binding only.
     W.forward(); W.keep_largest(fraction=0.05); W.inverse()   # best K-term approximation
     W = Wavelets3D(vol, "db4", 3, do_swt=1); W.forward(); W.soft_threshold(10); W.inverse()   # translation-invariant denoising
     W.group_soft_threshold(t); W.proj_linf(t); W.shrink(t); W.add_wavelet(W_old, -0.5); W.group_norm()   # the proximal steps
+    W = Wavelets3D(vol, "db4", 3); W.cycle_spin(n=8, beta=10); W.image   # cycle spinning: the mean of the denoiser over 8 shifts
 """
+import itertools
 import ctypes as C
 
 import numpy as np
@@ -45,6 +47,28 @@ def volume_layout_swt(shape, wname, levels, dtype=np.float32, lib=None):
     return nlev.value, nbytes.value
 
 
+def spin_footprint(shape, dtype=np.float32, lib=None):
+    """Bytes of device memory the first `Wavelets3D.cycle_spin` of a volume of `shape` and `dtype` allocates (the kept source and
+    the running mean: two volumes, each padded to 256 bytes): a pure host computation (pdwt_volume_spin_footprint)."""
+    lib = lib or _lib.load()
+    nz, nr, nc = (int(n) for n in shape)
+    out = C.c_size_t(0)
+    check(lib.pdwt_volume_spin_footprint(nz, nr, nc, np.dtype(dtype).itemsize, C.byref(out)), "spin_footprint", lib)
+    return int(out.value)
+
+
+def spin_lattice(n):
+    """The first `n` (at most 64) shifts (sz, sr, sc) of the fixed lattice of `Wavelets3D.cycle_spin`: the eight points of
+    {0, 1}^3 in lexicographic order -- (0,0,0), (0,0,1), (0,1,0), ..., (1,1,1) --, then the points of {0, 1, 2, 3}^3 in
+    lexicographic order without those eight.  An (n, 3) int32 array."""
+    n = int(n)
+    if not 1 <= n <= 64:
+        raise ValueError("spin_lattice: n must be 1 .. 64, got %d" % n)
+    first = list(itertools.product((0, 1), repeat=3))
+    rest = [p for p in itertools.product(range(4), repeat=3) if max(p) > 1]
+    return np.array((first + rest)[:n], dtype=np.int32)
+
+
 class Wavelets3D(object):
     """3D DWT plan of one volume [Nz][Nr][Nc].
 
@@ -61,6 +85,9 @@ class Wavelets3D(object):
           `threshold_bands`, `denoise`, `select_magnitude`, `keep_largest`, `norms_device`) are not built for it and raise
           NotImplementedError.
 
+    Cycle spinning -- a fresh random circular shift per ``forward()``, undone by ``inverse()``, as `Wavelets(do_cycle_spinning=1)`
+    does in 2D -- is turned on with ``set_cycle_spinning(1, seed)``; ``cycle_spin`` is the averaged denoiser.
+
     Coefficient index ``num``: 0 = the approximation A_L, then 1 + 7 (l - 1) + k with level 1 the FINEST and k over the keys
     'aad', 'ada', 'add', 'daa', 'dad', 'dda', 'ddd' -- pywt.wavedecn's, axes (z, y, x).  ``coeffs`` is ``[A, d_1, ..., d_L]``
     with every d_l a dict over those keys; pywt.wavedecn's order is ``[c[0]] + c[:0:-1]``.
@@ -71,6 +98,7 @@ class Wavelets3D(object):
     def __init__(self, vol, wname, levels, device=-1, stream=None, do_swt=0):
         self._h = None
         self.do_swt = 1 if do_swt else 0
+        self.do_cycle_spinning = 0
         self._lib = _lib.load(self._variant)
         dev = _device_array(vol, self._dtype)
         if dev is not None:
@@ -194,6 +222,63 @@ class Wavelets3D(object):
             print("Warning: " + _lib.last_error(self._lib))
             return
         self._check(rc, "inverse")
+
+    # ---- circular shifts and cycle spinning
+    def circshift(self, sz, sr, sc):
+        """image <- numpy.roll(image, (sz, sr, sc), axis=(0, 1, 2)), on the device and in place as the caller sees it
+        (``image_device`` stays where it is).  Shifts may be negative or beyond the size.  The image must be current: after
+        ``forward()`` it raises; run ``inverse()`` or ``set_image`` first."""
+        self._check(self._lib.pdwt_volume_circshift(self._h, int(sz), int(sr), int(sc)), "circshift")
+
+    def set_cycle_spinning(self, on=1, seed=None):
+        """``on``: every ``forward()`` first shifts the image circularly by a fresh pseudo-random (sz, sr, sc) and the matching
+        ``inverse()`` shifts the result back -- one random shift per iteration of an iterative reconstruction, what
+        `Wavelets(..., do_cycle_spinning=1)` does in 2D.  ``seed`` (None = 0) decides the draws: the same seed gives the same
+        shifts.  ``last_shift`` tells the shift.  Decimated volumes only (a stationary one raises NotImplementedError).  Off by
+        default.  Returns self."""
+        self._check(self._lib.pdwt_volume_set_cycle_spinning(self._h, 1 if on else 0, int(seed or 0) & (2 ** 64 - 1)), "set_cycle_spinning")
+        self.do_cycle_spinning = 1 if on else 0
+        return self
+
+    @property
+    def last_shift(self):
+        """(sz, sr, sc): what ``forward()`` shifted the image by (``set_cycle_spinning``; the sum of the draws when several
+        forwards ran in a row); (0, 0, 0) once ``inverse()`` has shifted back, after ``set_image`` and without cycle spinning."""
+        v = (C.c_int * 3)()
+        self._check(self._lib.pdwt_volume_current_shift(self._h, v), "last_shift")
+        return tuple(int(x) for x in v)
+
+    def cycle_spin(self, shifts=None, n=8, mode="soft", beta=None, method=None, sigma=None, do_threshold_appcoeffs=0, normalize=0,
+                   skip_zeros=True):
+        """Cycle spinning (Coifman and Donoho): image <- the mean over K circular shifts s of  unshift_s(inverse(theta(forward(
+        shift_s(image))))) -- the decimated denoiser made (nearly) translation invariant at K times its cost and two extra volumes
+        of memory (`spin_footprint`), all on the device.
+
+        shifts : (K, 3) integers (sz, sr, sc); None = the first ``n`` points of `spin_lattice` (n = 8: all shifts by 0 or 1)
+        mode : "soft" or "hard"
+        beta : the global threshold, as ``soft_threshold(beta, do_threshold_appcoeffs, normalize)`` / ``hard_threshold``;
+        method : instead of ``beta``, "BayesShrink" or "VisuShrink" as ``denoise(method, sigma, mode, skip_zeros)``: with
+                 ``sigma=None`` every shift estimates its own noise level.  Exactly one of ``beta`` and ``method``.
+        The image must be current (not after ``forward()``); afterwards the state is that after ``inverse()``.  Returns self; the
+        result is ``image``."""
+        if (beta is None) == (method is None):
+            raise ValueError("cycle_spin: expected exactly one of beta (a global threshold) and method (\"BayesShrink\" / \"VisuShrink\")")
+        op = self._choice(self._THRESHOLD_MODES, mode, "mode")
+        m = -1 if method is None else self._choice(self._DENOISE_METHODS, method, "method")
+        sh = spin_lattice(n) if shifts is None else np.ascontiguousarray(np.asarray(shifts))
+        if sh.dtype.kind not in "iu" or sh.ndim != 2 or sh.shape[1] != 3:
+            raise ValueError("cycle_spin: shifts must be a (K, 3) integer array, got %s %s" % (sh.dtype, sh.shape))
+        sh = np.ascontiguousarray(sh, dtype=np.int32)
+        arg = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(np.atleast_1d(np.asarray(sigma, dtype=np.float64)))
+            if sg.shape != (1,):
+                raise ValueError("cycle_spin: sigma must be one number (a volume is one image)")
+            arg = sg.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(self._lib.pdwt_volume_cycle_spin_async(self._h, sh.shape[0], sh.ctypes.data_as(C.POINTER(C.c_int)), op,
+                                                           float(beta) if beta is not None else 0.0, int(do_threshold_appcoeffs),
+                                                           int(normalize), m, arg, 1 if skip_zeros else 0), "cycle_spin")
+        return self
 
     # ---- data
     @property

@@ -41,6 +41,15 @@ approximation (8 B), two volumes read and one written for add_wavelet (12 B), 8 
 
     python tools/volbench.py --prox                > profiles/volume_proxbench.txt
 
+--spin: circular shifts and cycle spinning (Wavelets3D.cycle_spin) on 256^3 and 512^3 db4 with three levels, every line timed twice
+by device events after a warm-up: cycle_spin with 1 and with 8 lattice shifts and the soft threshold; in the same run the plain
+decimated forward + soft + inverse and (256^3 only by default: 27 volumes) the stationary forward + soft + inverse; the in-place
+circshift (the kernel plus the copy back).  The two kernels on their own, next to the flat copy of the same bytes in the same
+process, come from tools/volshiftbench.hip, which this mode builds with hipcc when tools/bin/volshiftbench is missing or older
+than its sources, on the same shapes and on 512 x 511 x 511 (value by value).
+
+    python tools/volbench.py --spin                > profiles/volume_spin_bench.txt
+
 --profile: a short run of ONE case with one level (so that every kernel name in the trace belongs to level 1) plus the copy and
 the 2D level of the same bytes, for rocprofv3; --summarize reads the kernel trace of such a run and reports, per depth kernel,
 its share of the copy next to the share the 2D level-1 kernel reaches.
@@ -387,6 +396,80 @@ def run_swt_summarize(args):
         print("  %-60s n=%4d median %9.2f us" % (k[:60], len(v), median(v)))
 
 
+SPIN_CASES = [("256^3 db4", (256, 256, 256), "db4", 3, True), ("512^3 db4", (512, 512, 512), "db4", 3, False)]
+SPIN_KERNEL_SHAPES = [(256, 256, 256), (512, 512, 512), (512, 511, 511)]
+
+
+def shift_bench_program():
+    """tools/bin/volshiftbench, built from tools/volshiftbench.hip when it is missing or older than what it includes."""
+    import shutil
+    import subprocess
+    src = os.path.join(ROOT, "tools", "volshiftbench.hip")
+    csrc = os.path.join(ROOT, "pypwt_amd", "csrc")
+    exe = os.path.join(ROOT, "tools", "bin", "volshiftbench")
+    deps = [src, os.path.join(csrc, "volume_shift_kernels.hpp"), os.path.join(csrc, "kernels_common.hpp")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(exe), exist_ok=True)
+        hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", csrc, src, "-o", exe])
+    return exe
+
+
+def run_spin(args):
+    import subprocess
+    from pypwt_amd.volume import spin_footprint, spin_lattice, volume_layout_swt
+    ev = Events()
+    print("# volbench --spin: cycle spinning of a volume, fp32, %d calls per timing after %d warm-up calls; every line timed twice" % (args.reps, args.warmup))
+    print("# %-11s %-34s %10s %10s %9s %9s" % ("case", "what", "ms (1st)", "ms (2nd)", "x 1 shift", "x swt"))
+    for k, (name, shape, wname, levels, with_swt) in enumerate(SPIN_CASES):
+        if args.case is not None and k != args.case:
+            continue
+        W = make_volume(shape, wname, levels)
+        lib, h = W._lib, W._h
+        lat = np.ascontiguousarray(spin_lattice(8))
+        sh = lat.ctypes.data_as(C.POINTER(C.c_int))
+
+        def ok(rc):
+            assert rc == 0, rc
+
+        def plain():
+            ok(lib.pdwt_volume_forward(h)), ok(lib.pdwt_volume_soft_threshold(h, 10.0, 0, 0)), ok(lib.pdwt_volume_inverse(h))
+
+        def spin(nshifts):
+            return lambda: ok(lib.pdwt_volume_cycle_spin_async(h, nshifts, sh, 0, 10.0, 0, 0, -1, None, 1))
+
+        def inplace():
+            ok(lib.pdwt_volume_circshift(h, 1, 2, 4))
+
+        got = {}
+        rows = [("forward + soft + inverse", plain), ("cycle_spin, 1 shift, soft", spin(1)), ("cycle_spin, 8 shifts, soft", spin(8)),
+                ("circshift in place (1, 2, 4)", inplace)]
+        for what, fn in rows:
+            t = [ev.time(W._stream(), fn, args.reps, args.warmup) for _ in range(2)]
+            got[what] = (t[0], t[1])
+        W.cleanup()
+        if with_swt:
+            S = make_volume(shape, wname, levels, do_swt=1)
+            fn = dict((v[0], v[1]) for v in variants(S))["fwd+soft+inv"]
+            t = [ev.time(S._stream(), fn, args.reps, args.warmup) for _ in range(2)]
+            got["stationary forward + soft + inverse"] = (t[0], t[1])
+            S.cleanup()
+        one = min(got["cycle_spin, 1 shift, soft"])
+        swt = min(got["stationary forward + soft + inverse"]) if with_swt else None
+        for what, t in got.items():
+            print("  %-11s %-34s %10.4f %10.4f %9.2f %9s" % (name, what, t[0], t[1], min(t) / one, "%9.2f" % (min(t) / swt) if swt else "-"))
+        vol = 4.0 * shape[0] * shape[1] * shape[2]
+        print("  %-11s device memory: decimated handle about 3.3 volumes + cycle_spin %.2f volumes; stationary handle %.1f volumes"
+              % (name, spin_footprint(shape, np.float32) / vol, volume_layout_swt(shape, wname, levels)[1] / vol))
+        sys.stdout.flush()
+    if args.case is None:
+        exe = shift_bench_program()
+        print("# the two kernels on their own (tools/volshiftbench.hip): ms (1st), ms (2nd), GB/s of the bytes moved, share of the same-run flat copy")
+        sys.stdout.flush()
+        for shape in SPIN_KERNEL_SHAPES:
+            subprocess.check_call([exe] + [str(n) for n in shape] + [str(args.reps), str(args.warmup)])
+
+
 def run_profile(args):
     name, shape, wname, _ = CASES[args.case]
     W = make_volume(shape, wname, 1)
@@ -434,6 +517,7 @@ def main():
     ap.add_argument("--ops", action="store_true")
     ap.add_argument("--swt", action="store_true")
     ap.add_argument("--prox", action="store_true")
+    ap.add_argument("--spin", action="store_true")
     ap.add_argument("--summarize", default=None)
     ap.add_argument("--list", action="store_true")
     args = ap.parse_args()
@@ -443,6 +527,8 @@ def main():
         return
     if args.prox:
         run_prox(args)
+    elif args.spin:
+        run_spin(args)
     elif args.swt:
         if args.summarize:
             run_swt_summarize(args)
