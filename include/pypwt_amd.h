@@ -192,7 +192,10 @@ int pdwt_select_magnitude_async(pdwt_handle h, const long long* k, int nk, int d
 int pdwt_keep_largest_async(pdwt_handle h, const long long* k, int nk, int do_thresh_appcoeffs);
 /* device addresses of the plan's own slots of the last of the two calls (either argument may be NULL) */
 int pdwt_sparsify_slots(pdwt_handle h, pdwt_real** d_threshold, unsigned long long** d_kept);
-/* dst += alpha * src ; returns 0, or the reference's codes -1..-4 / +1 (wt.cu:622-655) */
+/* dst += alpha * src ; returns 0, or the reference's codes -1..-4 / +1 (wt.cu:622-655).  On dst's stream, after the host has
+ * waited for src's.  KNOWN GAP when the two plans have different streams: what src's stream is given afterwards is NOT ordered
+ * after the sum's read of src -- wait for dst (pdwt_synchronize) before src is written again.  pdwt_volume_add_wavelet orders
+ * both ways. */
 int pdwt_add_wavelet(pdwt_handle dst, pdwt_handle src, pdwt_real alpha);
 
 /* ---- data movement (pdwt/src/wt.cu:419-506) ---- */
@@ -439,7 +442,8 @@ int pdwt_volume_read(pdwt_volume_handle h, void* dst, const void* d_src, long lo
  *     with do_thresh_appcoeffs;  pdwt_volume_shrink (wt.cu:340-347, common.cu:347-371): x * (1 / (1 + beta)), the factor formed
  *     once on the host in pdwt_real; same coverage.  The Python defaults are the reference's (pypwt.pyx:406);
  *   - pdwt_volume_add_wavelet (wt.cu:622-655, common.cu:499-526): c += alpha * c_src on all 1 + 7 L sub-bands, one fused
- *     multiply-add per value, on dst's stream, ordered after what is queued on src's stream.  Both handles must come from this
+ *     multiply-add per value, on dst's stream, ordered after what is queued on src's stream; what src's stream is given afterwards
+ *     waits until the sum has read src (nothing stops the host).  Both handles must come from this
  *     library (the same pdwt_real) and agree in shape, wavelet name, levels, transform kind and device: else PDWT_ERR_MISMATCH;
  *   - pdwt_volume_group_norm (no reference counterpart; pdwt/TODO.txt:14 asks for it): *out = the sum over levels and positions of
  *     ||g||_2, the l2,1 norm whose proximal map the group threshold is.  Every term in double (the members are converted, squared

@@ -701,6 +701,18 @@ int group_norm_entry(pdwt_volume_handle v, int do_app, double* d_out, double** d
     return PDWT_OK;
 }
 
+// what `later` is given from now on runs after what `earlier` holds now; the host does not wait
+int order_after(hipStream_t later, hipStream_t earlier) {
+    if (later == earlier) return PDWT_OK;
+    hipEvent_t done = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(done, earlier);
+    if (e == hipSuccess) e = hipStreamWaitEvent(later, done, 0);
+    (void)hipEventDestroy(done);  // (released once it has completed)
+    HIP_TRY(e);
+    return PDWT_OK;
+}
+
 // data into a sub-band or the image: nothing moves where the caller passes the destination itself
 int copy_in(pdwt_volume_handle v, real_t* dst, const pdwt_real* src, long long count, int mem_is_on_device) {
     if (mem_is_on_device && src == dst) return PDWT_OK;
@@ -1031,15 +1043,12 @@ int pdwt_volume_add_wavelet(pdwt_volume_handle dst, pdwt_volume_handle src, pdwt
     DeviceGuard guard(dst->device);
     PDWT_TRY(dst->enter_sweep("add_wavelet"));
     if (src != dst) PDWT_TRY(src->enter_sweep("add_wavelet"));
-    if (src->stream != dst->stream) {  // after what is queued on the source's stream, without stopping the host
-        hipEvent_t done = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(done, src->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, done, 0);
-        (void)hipEventDestroy(done);  // (released once it has completed)
-        HIP_TRY(e);
-    }
-    return dst->axpy(src, alpha);
+    // after what is queued on the source's stream, without stopping the host ...
+    PDWT_TRY(order_after(dst->stream, src->stream));
+    PDWT_TRY(dst->axpy(src, alpha));
+    // ... and whatever the source's stream is given next waits until the sum has read the source: the caller's next call on
+    // `src` (a threshold, a forward, set_coeff) would otherwise overwrite coefficients the sum is still reading
+    return order_after(src->stream, dst->stream);
 }
 
 int pdwt_volume_group_norm_async(pdwt_volume_handle v, int do_thresh_appcoeffs, double* d_out, double** d_slot) {
