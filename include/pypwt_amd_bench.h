@@ -117,7 +117,12 @@ int pdwt_set_tuning(const char* key, int value);
 /* One more key, kept beside the table above (csrc/tuning_knobs.inc says why) -- inv_coarse3: the inverse of the three coarsest
  * 2D DWT levels of a large plane in ONE launch (csrc/dwt2_inv_coarse_kernels.hpp; fp32 libraries, even filters of at most 8 taps).
  * 0: never; 1 (default): where that launch writes more than 2^20 and at most 2^22 samples over the batch (the 2048^2 plane of
- * one 4096^2 image); 2: wherever the kernel applies (tests).  Read when a plan is created, like the others. */
+ * one 4096^2 image); 2: wherever the kernel applies (tests).  Read when a plan is created, like the others.
+ * And wt_stores, kept the same way: the inverse coarse group writes its output with 16-B write-through stores, so that the next
+ * launch does not start behind an L2 full of dirty lines.  0: never; 1 (default): in plans of at most 2^24 samples over the batch
+ * (one 4096^2 image) where the launch writes at least 2^22 into 16-B aligned rows of whole 16-B groups; 2: wherever those
+ * preconditions hold (tests).  Read when a plan is created; a clone copies it.  wt_stores_launches returns the process-wide number
+ * of launches that stored this way and sets it to the value given (tests). */
 
 /* Test hooks of a volume (tests/test_gpu_volume_taps.py).  Custom filter banks on volumes are NOT part of the product: these
  * exist so that every depth-kernel instantiation can be run with a bank whose every tap counts, at every segment length.

@@ -22,6 +22,10 @@
 // LDS: [ (A,V)(l) | (H,D)(l) | tt(l) ] as in dwt2_inv_fast_tile; the coarse regions alias tt, which the level-l column
 // pass writes first -- after the last coarse read, with a barrier in between.
 //
+// The coarse row passes are inv_row_synth4 of the tile kernels: a work item is four adjacent outputs of a row, its window 16-B LDS
+// reads issued together, and it writes whole (A,V) pairs -- V of level l+1 from a plain plane staged where tt2 will be, V / H / D of
+// level l from the registers of the thread that has held them since phase 1 (the commit is part of the last row pass).
+//
 // Exactness (as the tile pyramid): values at positions outside a plane are computed from periodically wrapped
 // coefficients, which equals the reference's per-level periodization when all three levels have even sizes.  The host
 // (launch_dwt2_inv_coarse.hip: dwt2_inv_coarse3_supported) also requires whole 16-B groups per row at all three levels
@@ -41,6 +45,7 @@ struct InvCoarse3Args {
     long long l3_bstride, l2_bstride, l1_bstride, out_bstride;
     int tiles_x, tiles_y;            // level-l coefficient tile grid (TX x TY)
     FilterBankI fb;                  // (rec_lo, rec_hi)
+    int wt_out = 0;                  // uniform: the output leaves as 16-B write-through stores (launch.hpp: wt_stores_take)
 };
 
 constexpr int inv_coarse_floor2(int v) { return v >= 0 ? v / 2 : -((1 - v) / 2); }
@@ -77,67 +82,83 @@ struct InvCoarse3Geom {
     static constexpr int TT = 2 * (2 * TY) * W1;                   // (t1,t2) pairs of level l
     static constexpr int O_AV2 = BASE, O_HD2 = O_AV2 + 2 * R2 * W2, O_TT2 = O_HD2 + 2 * R2 * W2;   // level l+1; tt2: R1 x W2
     static constexpr int O_AV3 = O_TT2 + 2 * R1 * W2, O_HD3 = O_AV3 + 2 * R3 * W3, O_TT3 = O_HD3 + 2 * R3 * W3;  // tt3: R2 x W3
-    static constexpr int COARSE = O_TT3 + 2 * R2 * W3 - BASE;
+    // (+ 4: the row synthesis reads whole 16-B groups, up to two (t1,t2) pairs past the last one it uses -- behind the last row of tt3)
+    static constexpr int COARSE = O_TT3 + 2 * R2 * W3 + 4 - BASE;
     static constexpr int LDS_FLOATS = BASE + (TT > COARSE ? TT : COARSE);
+    // the V band of level l+1 waits as a plain R2 x W2 plane where tt2 will be (nobody touches tt2 before the second stage)
+    static constexpr int O_V2 = O_TT2;
+    static_assert(R2 * W2 <= 2 * R1 * W2, "the plain V plane of level l+1 fits the (t1,t2) plane it borrows");
     static_assert((HLEN & 1) == 0 && HLEN >= 2, "even filters");
     static_assert((TY % 4) == 0 && (TX % 16) == 0, "tile bases are whole samples, and multiples of 4 columns, at all three levels");
     static_assert((X1 & 3) == 0 && (W1 & 3) == 0, "the level-l region is whole 16-B groups");
 };
 
-// Column synthesis then row synthesis of one stage, out of LDS: the (A,V) / (H,D) pairs of the input region (RI x WI at
-// (YI, XI)) give the A lanes of the output region (RO x WO at (YO, XO)); tt holds RO x WI (t1,t2) pairs in between.  The
-// V lanes of the output's (A,V) plane were staged from global memory and are left alone.
+// One synthesis stage out of LDS: the (A,V) / (H,D) pairs of the input region (RI x WI at (YI, XI)) give the A values of the
+// output region (RO x WO at (YO, XO)); tt holds RO x WI (t1,t2) pairs in between.  Column pass (inv_coarse_cols), a barrier,
+// row pass (inv_coarse_row4 inside inv_coarse_rows / the tile's last stage).
 template <int HLEN, int NT, int RI, int WI, int YI, int XI, int RO, int WO, int YO, int XO>
-PDWT_DEVICE void inv_coarse_synth(const v2f* sAVi, const v2f* sHDi, v2f* tti, v2f* sAVo, const FilterBankI& fb) {
+PDWT_DEVICE void inv_coarse_cols(int tid, const v2f* sAVi, const v2f* sHDi, v2f* tti, const FilterBankI& fb) {
     using AY = InvCoarseAxis<HLEN, YO, RO, false>;
     using AX = InvCoarseAxis<HLEN, XO, WO, false>;
-    constexpr int H = HLEN, H2 = AY::H2, C = AY::C, S = AY::S;
+    constexpr int H = HLEN, C = AY::C, S = AY::S;
     static_assert(AY::I >= YI && AY::I + AY::M <= YI + RI && AX::I >= XI && AX::I + AX::M <= XI + WI, "the input region covers the stage");
-    PDWT_FOR_THREADS(tid, NT) {
-        constexpr int Q2 = WI / 2;
-        for (int idx = tid; idx < AY::NK * Q2; idx += NT) {
-            const int ki = idx / Q2, q = 2 * (idx - ki * Q2);
-            const int kk = AY::K_LO + ki;
-            v2f e0, o0, e1, o1;
-            inv_col_synth2<H>(&sAVi[(kk - C - YI) * WI + q], &sHDi[(kk - C - YI) * WI + q], WI, fb, e0, o0, e1, o1);
-            const int ge = 2 * kk - S - YO, go = ge + 1;  // local output rows
-            f32x4 w;
-            if (ge >= 0 && ge < RO) {
-                w.x = e0.x; w.y = e0.y; w.z = e1.x; w.w = e1.y;
-                *reinterpret_cast<f32x4*>(&tti[ge * WI + q]) = w;
-            }
-            if (go >= 0 && go < RO) {
-                w.x = o0.x; w.y = o0.y; w.z = o1.x; w.w = o1.y;
-                *reinterpret_cast<f32x4*>(&tti[go * WI + q]) = w;
-            }
+    constexpr int Q2 = WI / 2;
+    for (int idx = tid; idx < AY::NK * Q2; idx += NT) {
+        const int ki = idx / Q2, q = 2 * (idx - ki * Q2);
+        const int kk = AY::K_LO + ki;
+        v2f e0, o0, e1, o1;
+        inv_col_synth2<H>(&sAVi[(kk - C - YI) * WI + q], &sHDi[(kk - C - YI) * WI + q], WI, fb, e0, o0, e1, o1);
+        const int ge = 2 * kk - S - YO, go = ge + 1;  // local output rows
+        f32x4 w;
+        if (ge >= 0 && ge < RO) {
+            w.x = e0.x; w.y = e0.y; w.z = e1.x; w.w = e1.y;
+            *reinterpret_cast<f32x4*>(&tti[ge * WI + q]) = w;
+        }
+        if (go >= 0 && go < RO) {
+            w.x = o0.x; w.y = o0.y; w.z = o1.x; w.w = o1.y;
+            *reinterpret_cast<f32x4*>(&tti[go * WI + q]) = w;
         }
     }
-    PDWT_SYNC();
-    PDWT_FOR_THREADS(tid, NT) {
-        for (int idx = tid; idx < RO * AX::NK; idx += NT) {
-            const int r = idx / AX::NK, kk = AX::K_LO + (idx - r * AX::NK);
-            const v2f* u = tti + r * WI + (kk - C - XI);
-            v2f re = mk2(0.f, 0.f), ro = mk2(0.f, 0.f);
-#pragma unroll
-            for (int j = 0; j < H2; ++j) {
-                const v2f w = u[j];
-                re = fma2(w, fb.t[H - 2 - 2 * j], re);
-                ro = fma2(w, fb.t[H - 1 - 2 * j], ro);
-            }
-            const int ge = 2 * kk - S - XO, go = ge + 1;  // local output columns
-            if (ge >= 0 && ge < WO) sAVo[r * WO + ge].x = re.x + re.y;
-            if (go >= 0 && go < WO) sAVo[r * WO + go].x = ro.x + ro.y;
-        }
+}
+
+// Row synthesis of a stage, one work item = output row r x output columns 4g .. 4g + 3 (local): inv_row_synth4 on the two
+// coefficient columns (XO + 4g) / 2, + 1 of the input level -- the window in 16-B LDS reads issued together, each output summed in
+// the order of the tile kernels' row pass.  XO and XI are multiples of 4, so the window's origin has the parity of C and is
+// rounded down to an even pair (PE); it may reach up to two pairs past the last one used (InvCoarse3Geom::COARSE has room).
+template <int HLEN, int WI, int XI, int XO>
+PDWT_DEVICE void inv_coarse_row4(const v2f* tti, int r, int g, const FilterBankI& fb, real_t res[4]) {
+    constexpr int C = (HLEN / 2) / 2, PE = C & 1;
+    static_assert((XI & 3) == 0 && (XO & 3) == 0 && (WI & 3) == 0, "whole 16-B groups");
+    static_assert(XO / 2 - C - XI - PE >= 0, "the window starts inside the staged row");
+    const int k = (XO + 4 * g) / 2;  // (a multiple of 4 halved: exact for a negative origin too)
+    inv_row_synth4<HLEN, PE>(tti + r * WI + (k - C - XI - PE), fb, res);
+}
+
+// ... of a stage whose output level has its V band waiting as a plain RO x WO plane in LDS: whole (A,V) pairs leave as 16-B writes
+template <int HLEN, int NT, int WI, int XI, int RO, int WO, int XO>
+PDWT_DEVICE void inv_coarse_rows(int tid, const v2f* tti, const real_t* sV, v2f* sAVo, const FilterBankI& fb) {
+    constexpr int V4 = WO / 4;
+    for (int idx = tid; idx < RO * V4; idx += NT) {
+        const int r = idx / V4, g = idx - r * V4;
+        real_t res[4];
+        inv_coarse_row4<HLEN, WI, XI, XO>(tti, r, g, fb, res);
+        const v4f v = lds_load16(sV + r * WO + 4 * g);
+        f32x4 w;
+        f32x4* d = reinterpret_cast<f32x4*>(sAVo + r * WO + 4 * g);
+        w.x = res[0]; w.y = v.x; w.z = res[1]; w.w = v.y; d[0] = w;
+        w.x = res[2]; w.y = v.z; w.z = res[3]; w.w = v.w; d[1] = w;
     }
 }
 
 // Stage R x W coefficients of up to four planes at (y0, x0) of an (Nr, Nc) level: 16-B loads, a constant number of trips, the
 // index clamped (the surplus threads write the last group again, with the same values) and wrapped by one conditional add / sub
 // (Nr >= R, Nc >= W, x0 and Nc multiples of 4: a group never straddles the wrap) -- nothing between a thread's loads makes one
-// wait for another.  WITH_A: the A plane too, interleaved as in dwt2_inv_fast_tile; otherwise only the V lanes of (A,V).
+// wait for another.  WITH_A: the A plane too, interleaved as in dwt2_inv_fast_tile; otherwise V goes to the plain plane sV (one 16-B
+// write per group), where the row pass that synthesises this level's A finds it (inv_coarse_rows).
 template <int NT, int R, int W, bool WITH_A>
 PDWT_DEVICE void inv_coarse_stage(int tid, const float* PDWT_RESTRICT pA, const float* PDWT_RESTRICT pH, const float* PDWT_RESTRICT pV,
-                                  const float* PDWT_RESTRICT pD, long long boff, int y0, int x0, int Nr, int Nc, v2f* sAV, v2f* sHD) {
+                                  const float* PDWT_RESTRICT pD, long long boff, int y0, int x0, int Nr, int Nc, v2f* sAV, v2f* sHD,
+                                  float* sV = nullptr) {
     constexpr int V4 = W / 4, TOTAL = R * V4, TRIPS = (TOTAL + NT - 1) / NT;
 #pragma unroll
     for (int t = 0; t < TRIPS; ++t) {
@@ -154,8 +175,7 @@ PDWT_DEVICE void inv_coarse_stage(int tid, const float* PDWT_RESTRICT pA, const 
         if (WITH_A) {
             inv_fast_interleave(sAV, sHD, r * W + 4 * g, *reinterpret_cast<const v4f*>(pA + o), vV, vH, vD);
         } else {
-            v2f* dAV = sAV + r * W + 4 * g;
-            dAV[0].y = vV.x; dAV[1].y = vV.y; dAV[2].y = vV.z; dAV[3].y = vV.w;
+            *reinterpret_cast<v4f*>(sV + r * W + 4 * g) = vV;
             f32x4 w;
             f32x4* dHD = reinterpret_cast<f32x4*>(sHD + r * W + 4 * g);
             w.x = vH.x; w.y = vD.x; w.z = vH.y; w.w = vD.y; dHD[0] = w;
@@ -190,18 +210,24 @@ PDWT_DEVICE void inv_coarse_issue(int tid, const float* PDWT_RESTRICT pH, const 
     }
 }
 
-template <int NT, int R, int W>
-PDWT_DEVICE void inv_coarse_commit(int tid, const v4f* held, v2f* sAV, v2f* sHD) {
+// The row pass of the LAST stage and the commit in one: a thread's work items are the groups whose level-l details it has held
+// since phase 1 -- their A values from inv_coarse_row4, V / H / D from its registers -- so whole (A,V) and (H,D) pairs leave as
+// 16-B writes and no A plane waits in LDS for another thread.
+template <int HLEN, int NT, int WI, int XI, int R, int W, int XO>
+PDWT_DEVICE void inv_coarse_rows_commit(int tid, const v2f* tti, const v4f* held, v2f* sAV, v2f* sHD, const FilterBankI& fb) {
     using T = InvCoarseHeld<NT, R, W>;
 #pragma unroll
     for (int t = 0; t < T::TRIPS; ++t) {
         int idx = tid + t * NT;
         idx = idx < T::TOTAL ? idx : T::TOTAL - 1;
         const int r = idx / T::V4, g = idx - r * T::V4;
+        real_t res[4];
+        inv_coarse_row4<HLEN, WI, XI, XO>(tti, r, g, fb, res);
         const v4f vV = held[3 * t + 0], vH = held[3 * t + 1], vD = held[3 * t + 2];
-        v2f* dAV = sAV + r * W + 4 * g;
-        dAV[0].y = vV.x; dAV[1].y = vV.y; dAV[2].y = vV.z; dAV[3].y = vV.w;
         f32x4 w;
+        f32x4* dAV = reinterpret_cast<f32x4*>(sAV + r * W + 4 * g);
+        w.x = res[0]; w.y = vV.x; w.z = res[1]; w.w = vV.y; dAV[0] = w;
+        w.x = res[2]; w.y = vV.z; w.z = res[3]; w.w = vV.w; dAV[1] = w;
         f32x4* dHD = reinterpret_cast<f32x4*>(sHD + r * W + 4 * g);
         w.x = vH.x; w.y = vD.x; w.z = vH.y; w.w = vD.y; dHD[0] = w;
         w.x = vH.z; w.y = vD.z; w.z = vH.w; w.w = vD.w; dHD[1] = w;
@@ -220,6 +246,7 @@ PDWT_DEVICE void dwt2_inv_coarse3_tile(const InvCoarse3Args& a, int bx, int by, 
     v2f* sAV2 = reinterpret_cast<v2f*>(smem + P::O_AV2);  // the coarse regions alias tt
     v2f* sHD2 = reinterpret_cast<v2f*>(smem + P::O_HD2);
     v2f* tt2 = reinterpret_cast<v2f*>(smem + P::O_TT2);
+    float* sV2 = smem + P::O_V2;  // the plain V plane of level l+1, until phase 3 has read it
     v2f* sAV3 = reinterpret_cast<v2f*>(smem + P::O_AV3);
     v2f* sHD3 = reinterpret_cast<v2f*>(smem + P::O_HD3);
     v2f* tt3 = reinterpret_cast<v2f*>(smem + P::O_TT3);
@@ -232,17 +259,26 @@ PDWT_DEVICE void dwt2_inv_coarse3_tile(const InvCoarse3Args& a, int bx, int by, 
         inv_coarse_stage<NT, P::R3, P::W3, true>(tid, a.A3, a.H3, a.V3, a.D3, (long long)bz * a.l3_bstride, by * (TY / 4) + P::Y3,
                                                  bx * (TX / 4) + P::X3, N3r, N3c, sAV3, sHD3);
         inv_coarse_stage<NT, P::R2, P::W2, false>(tid, nullptr, a.H2, a.V2, a.D2, (long long)bz * a.l2_bstride, by * (TY / 2) + P::Y2,
-                                                  bx * (TX / 2) + P::X2, N2r, N2c, sAV2, sHD2);
+                                                  bx * (TX / 2) + P::X2, N2r, N2c, sAV2, sHD2, sV2);
         inv_coarse_issue<NT, P::R1, P::W1>(tid, a.H1, a.V1, a.D1, (long long)bz * a.l1_bstride, by * TY + P::Y1, bx * TX + P::X1, N1r,
                                            N1c, PDWT_MINE(held, tid));
     }
     PDWT_SYNC();
-    // ---- phases 2, 3: level l+2 -> A(l+1); phases 4, 5: level l+1 -> A(l), a barrier between every two
-    inv_coarse_synth<HLEN, NT, P::R3, P::W3, P::Y3, P::X3, P::R2, P::W2, P::Y2, P::X2>(sAV3, sHD3, tt3, sAV2, a.fb);
+    // ---- phases 2, 3: level l+2 -> (A,V)(l+1); phases 4, 5: level l+1 -> (A,V)(l), a barrier between every two
+    PDWT_FOR_THREADS(tid, NT) {
+        inv_coarse_cols<HLEN, NT, P::R3, P::W3, P::Y3, P::X3, P::R2, P::W2, P::Y2, P::X2>(tid, sAV3, sHD3, tt3, a.fb);
+    }
     PDWT_SYNC();
-    inv_coarse_synth<HLEN, NT, P::R2, P::W2, P::Y2, P::X2, P::R1, P::W1, P::Y1, P::X1>(sAV2, sHD2, tt2, sAV, a.fb);
-    // ... and the details of level l, held in registers since phase 1, beside the A lanes that phase 5 wrote
-    PDWT_FOR_THREADS(tid, NT) { inv_coarse_commit<NT, P::R1, P::W1>(tid, PDWT_MINE(held, tid), sAV, sHD); }
+    PDWT_FOR_THREADS(tid, NT) { inv_coarse_rows<HLEN, NT, P::W3, P::X3, P::R2, P::W2, P::X2>(tid, tt3, sV2, sAV2, a.fb); }
+    PDWT_SYNC();
+    PDWT_FOR_THREADS(tid, NT) {  // (tt2 overwrites the plain V plane, which phase 3 has merged into sAV2)
+        inv_coarse_cols<HLEN, NT, P::R2, P::W2, P::Y2, P::X2, P::R1, P::W1, P::Y1, P::X1>(tid, sAV2, sHD2, tt2, a.fb);
+    }
+    PDWT_SYNC();
+    // ... with the details of level l, held in registers since phase 1, beside the A values of their own groups
+    PDWT_FOR_THREADS(tid, NT) {
+        inv_coarse_rows_commit<HLEN, NT, P::W2, P::X2, P::R1, P::W1, P::X1>(tid, tt2, PDWT_MINE(held, tid), sAV, sHD, a.fb);
+    }
     PDWT_SYNC();
 
     // ---- phases 6, 7: the ordinary level-l inverse tile (tt overwrites the coarse regions: nobody reads them any more)
@@ -256,7 +292,7 @@ PDWT_DEVICE void dwt2_inv_coarse3_tile(const InvCoarse3Args& a, int bx, int by, 
     PDWT_SYNC();
     PDWT_FOR_THREADS(tid, NT) {
         f.fb = a.fb;
-        inv_fast_row_pass<HLEN, TX, TY, NT>(tid, tt, f, bx, by, bz);
+        inv_fast_row_pass<HLEN, TX, TY, NT>(tid, tt, f, bx, by, bz, a.wt_out != 0);
     }
 }
 

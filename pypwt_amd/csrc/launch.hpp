@@ -116,6 +116,24 @@ hipError_t launch_dwt2_inv_coarse3(const real_t* app, real_t* const det[9], real
 // pdwt_set_tuning("inv_coarse3"): 0 never, 1 the size rule of build_schedule, 2 wherever supported (tests); read when a plan is built
 int inv_coarse3_mode();
 int set_inv_coarse3_mode(int v);  // returns the previous value
+// pdwt_set_tuning("wt_stores"): whole-line write-through (sc1) stores for a launch whose output the NEXT launch reads while the plan is
+// cache-resident -- the inverse coarse group of one large image (launch_dwt2.hip: wt_stores_take has the rule).  0 never, 1 the
+// size rule, 2 wherever the preconditions hold (tests).  A plan keeps the value it was created with
+// (pdwt_plan::wt_stores) and makes it the calling thread's active value around its launches; with no active value (direct calls of
+// the launchers) the stores are plain.  fp32 libraries only.
+int wt_stores_mode();
+int set_wt_stores_mode(int v);       // returns the previous value
+int set_wt_stores_launches(int v);   // the process-wide count of launches that took the policy: sets it, returns the previous count
+void set_active_wt_stores(int mode);  // thread-local
+int active_wt_stores();
+struct ActiveWtStores {  // RAII, beside ActiveTuning
+    int prev;
+    explicit ActiveWtStores(int mode) : prev(active_wt_stores()) { set_active_wt_stores(mode); }
+    ~ActiveWtStores() { set_active_wt_stores(prev); }
+};
+// the launcher's question: does this launch, which writes batch x (Nr, Nc) samples to `out` (images bstride elements apart), store
+// write-through?  Counts the launch when it answers yes, so ask once per launch.
+bool wt_stores_take(const void* out, int Nr, int Nc, long long bstride, int batch);
 // ALL remaining levels of small approximations in one launch, one workgroup per image (launch_dwt2_tail.hip): (R0, C0) enter
 // the group's finest level (at most 16384 samples, fp64 8192; even sizes at every level's input: powers of two or not), det[3 k + b] = band b of the
 // group's k-th level (finest first); forward: in = A_{l-1}, out = A_L; inverse: in = A_L, out = A_{l-1}

@@ -141,6 +141,45 @@ Tuning current_tuning() {
     return t;
 }
 
+// ---- "wt_stores" (beside the table, like "inv_coarse3"): write-through stores for launches that end a one-round latency chain.
+// A dependent launch boundary costs an extra B / 6 TB/s when the predecessor leaves B bytes dirty in the XCDs' L2s; 16-B sc1 stores
+// send the lines on as they are written, so the next launch starts behind a drained L2 (profiles/wt_stores_ab.txt).  That pays for
+// ONE cache-resident image whose launches are single rounds; on a batch the L2's write combining matters more than the tail (round
+// 3), hence the size rule: plans of at most 2^wt_stores_max_log2 samples over the batch (plan.cpp: inverse_impl clears the active
+// value for larger ones), in launches that write at least 2^wt_stores_min_log2 -- the one plane it was measured on.  The inverse
+// coarse group asks (launch_dwt2_inv_coarse.hip); the level-1 inverse tile lost its A/B and does not.
+#ifdef PDWT_DOUBLE
+int wt_stores_mode() { return 0; }
+int set_wt_stores_mode(int) { return 0; }
+int set_wt_stores_launches(int) { return 0; }
+void set_active_wt_stores(int) {}
+int active_wt_stores() { return 0; }
+bool wt_stores_take(const void*, int, int, long long, int) { return false; }
+#else
+static std::atomic<int>& wt_mode() {
+    static std::atomic<int> v{lab_env("PDWT_WT_STORES") ? atoi(lab_env("PDWT_WT_STORES")) : 1};
+    return v;
+}
+static std::atomic<int> g_wt_launches{0};
+static thread_local int g_active_wt_stores = 0;
+int wt_stores_mode() { return wt_mode().load(std::memory_order_relaxed); }
+int set_wt_stores_mode(int v) { return wt_mode().exchange(v < 0 ? 0 : (v > 2 ? 2 : v)); }
+int set_wt_stores_launches(int v) { return g_wt_launches.exchange(v < 0 ? 0 : v); }
+void set_active_wt_stores(int mode) { g_active_wt_stores = mode; }
+int active_wt_stores() { return g_active_wt_stores; }
+bool wt_stores_take(const void* out, int Nr, int Nc, long long bstride, int batch) {
+    const int mode = g_active_wt_stores;
+    if (mode <= 0) return false;
+    // coh_store16: 16-B groups at a 32-bit byte offset from the image's own base
+    if ((reinterpret_cast<uintptr_t>(out) & 15) || (Nc & 3) || (bstride & 3)) return false;
+    if ((long long)Nr * Nc * (long long)sizeof(real_t) > 0xffffffffLL - 15) return false;
+    const long long samples = (long long)batch * Nr * Nc;
+    if (mode < 2 && (samples < (1LL << tune::wt_stores_min_log2) || samples > (1LL << tune::wt_stores_max_log2))) return false;
+    g_wt_launches.fetch_add(1, std::memory_order_relaxed);
+    return true;
+}
+#endif
+
 // Register-ring kernels (dwt2_ring_kernels.hpp): 38 % fewer vector instructions than the LDS tile at 16 taps (rocprofv3
 // SQ_INSTS_VALU per 4096^2 level: 11.1e6 -> 6.9e6, profiles/r05a_*), but a level is only as fast as its wavefronts are many:
 // same-box A/B inside plans (tools/ring_ab.py, profiles/r05c_ring_ab.txt; forward + inverse of the whole plan, tiles -> ring):

@@ -121,6 +121,7 @@ hipError_t launch_dwt2_inv_coarse3(const float* app, float* const det[9], float*
         a.fb.t[i].x = fb.lo[i];
         a.fb.t[i].y = fb.hi[i];
     }
+    a.wt_out = wt_stores_take(out, N0r, N0c, a.out_bstride, batch) ? 1 : 0;
     const Coarse3Shape* t = coarse3_table(hlen);
     static const int forced = lab_env("PDWT_INV_COARSE3_TILE") ? atoi(lab_env("PDWT_INV_COARSE3_TILE")) : 0;
     if (forced >= 1 && forced <= kCoarse3Shapes && t[forced - 1].fits(N0r, N0c)) return t[forced - 1].run(a, batch, s);

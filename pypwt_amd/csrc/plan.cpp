@@ -370,6 +370,7 @@ int create_impl(const real_t* img, int batch, int Nr, int Nc, const char* wname,
     if ((rc = build_layout(p)) != PDWT_OK) return bail(rc);
     p->tune = current_tuning();
     p->inv_coarse3 = inv_coarse3_mode();
+    p->wt_stores = wt_stores_mode();
     build_schedule(p);
     if (img) {
         hipError_t e = hipMemcpyAsync(p->image(), img, (size_t)batch * Nr * Nc * sizeof(real_t),
@@ -1021,6 +1022,9 @@ int forward_impl(pdwt_plan* p, int only = 0) {
 int inverse_impl(pdwt_plan* p, int only = 0) {
     using pdwt::Step;
     const ActiveTuning tuning_guard(&p->tune);
+    // (the size rule speaks of a cache-resident PLAN: the coarse levels of a batch are small launches too, yet the batch streams from HBM)
+    const bool wt_resident = (long long)p->batch * p->info.Nr * p->info.Nc <= (1LL << tune::wt_stores_max_log2);
+    const ActiveWtStores wt_guard(p->wt_stores == 1 && !wt_resident ? 0 : p->wt_stores);
     const int B = p->batch, hlen = p->info.hlen;
     const bool two_d = p->info.ndims == 2;
     const bool swt = p->info.do_swt != 0;
@@ -1534,6 +1538,7 @@ int pdwt_clone(pdwt_handle src, pdwt_handle* out) {
     if (rc != PDWT_OK) { pdwt_destroy(p); return rc; }
     p->tune = src->tune;
     p->inv_coarse3 = src->inv_coarse3;
+    p->wt_stores = src->wt_stores;
     build_schedule(p);  // not copied: a chain step needs the clone's own hand-off flags
     e = hipStreamSynchronize(src->stream);
     if (e == hipSuccess)
@@ -2302,6 +2307,9 @@ int pdwt_set_tuning(const char* key, int value) {
     if (key && !strcmp(key, "chain_timeout")) return set_chain_timeout(value);  // not a dispatch knob, not part of the snapshot
     // (tuning_knobs.inc says why this one is not a row; a plan keeps the value it was built with: pdwt_plan::inv_coarse3)
     if (key && !strcmp(key, "inv_coarse3")) return set_inv_coarse3_mode(value);
+    // (likewise: pdwt_plan::wt_stores; the second key is the count of launches that stored write-through -- tests)
+    if (key && !strcmp(key, "wt_stores")) return set_wt_stores_mode(value);
+    if (key && !strcmp(key, "wt_stores_launches")) return set_wt_stores_launches(value);
     return fail(PDWT_ERR_ARG, "pdwt_set_tuning: unknown key %s", key ? key : "(null)");
 }
 

@@ -135,6 +135,7 @@ struct pdwt_plan {
     std::vector<pdwt::Step> sched_fwd, sched_inv;  // launch lists, in execution order
     pdwt::Tuning tune{};  // the dispatch knobs as they stood when the plan was created (launch.hpp: ActiveTuning)
     int inv_coarse3 = 0;  // ... and the "inv_coarse3" key (launch.hpp: inv_coarse3_mode), which is not a row of the table
+    int wt_stores = 0;    // ... and the "wt_stores" key (launch.hpp: wt_stores_mode), likewise; active around the plan's launches
     // Step::CHAIN (several levels in one launch, dwt2_chain_kernels.hpp): per-tile hand-off flags of the forward and of the
     // inverse chain, batch x chain_tiles words each, zeroed once; every launch stamps them with a new epoch
     unsigned* chain_flags = nullptr;

@@ -51,6 +51,8 @@ PDWT_TUNE(pyr3_image_log2,      19, "profiles/r02y_pyr3_sweep.txt",           "r
 PDWT_TUNE(pyr3_image_long_log2, 18, "profiles/r02y_pyr3_sweep.txt",           "round 2",           "... 2^v for 10-16 taps (sym8 512^2 L3 21.6 vs 25.0 us; 1024 x 512: 37.3 vs 25.4)")
 PDWT_TUNE(inv_coarse3_above_log2, 20, "profiles/r07_inv_coarse3_ab.txt",      "round 7, 2026-10-20", "inverse only: the three coarsest levels of a large plane in one launch where it writes more than 2^v samples over the batch (up to there: the pyr3 / pyr2 rules above) ...")
 PDWT_TUNE(inv_coarse3_max_log2, 22, "profiles/r07_inv_coarse3_ab.txt",        "round 7, 2026-10-20", "... and at most 2^v (the 2048^2 plane of one 4096^2 image); tuning key inv_coarse3")
+PDWT_TUNE(wt_stores_max_log2,   24, "profiles/wt_stores_ab.txt",              "round 8, 2026-10-21", "write-through (sc1) 16-B stores in the inverse coarse group (11.4 -> 9.3 us) of plans of at most 2^v samples over the batch (one 4096^2 image; batches keep the L2's write combining); tuning key wt_stores")
+PDWT_TUNE(wt_stores_min_log2,   22, "profiles/wt_stores_ab.txt",              "round 8, 2026-10-21", "... in the launches that write at least 2^v samples (the 2048^2 plane the coarse group of that image writes)")
 PDWT_TUNE(strip2_min_log2,      26, "profiles/r01f_kbench_strip.txt",         "round 1",           "streaming strips (two forward levels per launch) from 2^v samples (8 x 4096^2: 284 -> 232 us)")
 PDWT_TUNE(strip2_min_log2_haar, 25, "profiles/r04za_ab_batchrange.txt",         "round 4",           "... 2-tap filters from 2^v (8 x 2048^2 63 -> 56 us)")
 PDWT_TUNE(tail_work_log2,       14, "profiles/r04zb_tailbench.txt",           "round 4",           "one-workgroup tail: planes of at most 2^v samples x taps ...")

@@ -42,3 +42,7 @@ PDWT_KNOB(reg1d,         0, 15, lab_env("PDWT_REG1D") ? (atoi(lab_env("PDWT_REG1
 // 2 wherever the kernel applies (tests).  The rows above are pinned one by one to the setters they replaced (tests/test_abi_cpu.py:
 // KNOB_RECORD, sixteen rows), so a key that never had such a setter lives in launch_dwt2_inv_coarse.hip (set_inv_coarse3_mode) and in
 // the plan (pdwt_plan::inv_coarse3: a clone rebuilds its launch lists from its source's value).
+// "wt_stores" (0, 2; initially 1; PDWT_WT_STORES in the measurement library) is kept the same way (launch_dwt2.hip: set_wt_stores_mode,
+// pdwt_plan::wt_stores): 16-B write-through stores in the inverse coarse group -- 0 never, 1 in plans of at most 2^wt_stores_max_log2
+// samples where the launch writes at least 2^wt_stores_min_log2 (tuning_gfx950.inc), 2 wherever the stores' preconditions hold
+// (tests).  "wt_stores_launches" reads (and sets) the process-wide count of launches that took it: not a dispatch key.
