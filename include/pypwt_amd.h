@@ -192,10 +192,9 @@ int pdwt_select_magnitude_async(pdwt_handle h, const long long* k, int nk, int d
 int pdwt_keep_largest_async(pdwt_handle h, const long long* k, int nk, int do_thresh_appcoeffs);
 /* device addresses of the plan's own slots of the last of the two calls (either argument may be NULL) */
 int pdwt_sparsify_slots(pdwt_handle h, pdwt_real** d_threshold, unsigned long long** d_kept);
-/* dst += alpha * src ; returns 0, or the reference's codes -1..-4 / +1 (wt.cu:622-655).  On dst's stream, after the host has
- * waited for src's.  KNOWN GAP when the two plans have different streams: what src's stream is given afterwards is NOT ordered
- * after the sum's read of src -- wait for dst (pdwt_synchronize) before src is written again.  pdwt_volume_add_wavelet orders
- * both ways. */
+/* dst += alpha * src ; returns 0, or the reference's codes -1..-4 / +1 (wt.cu:622-655).  On dst's stream, and ordered both ways
+ * with events when the two plans have different streams, as pdwt_volume_add_wavelet is: the sum runs after what src's stream
+ * holds, and what src's stream is given afterwards runs after the sum has read src.  The host waits for neither. */
 int pdwt_add_wavelet(pdwt_handle dst, pdwt_handle src, pdwt_real alpha);
 
 /* ---- data movement (pdwt/src/wt.cu:419-506) ---- */

@@ -1428,6 +1428,18 @@ int copy_in(pdwt_plan* p, real_t* dst, const real_t* src, long long n, int mem_i
     return PDWT_OK;
 }
 
+// what `later` is given from now on runs after what `earlier` holds now; the host does not wait (volume.cpp has its twin)
+int order_after(hipStream_t later, hipStream_t earlier) {
+    if (later == earlier) return PDWT_OK;
+    hipEvent_t done = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(done, earlier);
+    if (e == hipSuccess) e = hipStreamWaitEvent(later, done, 0);
+    (void)hipEventDestroy(done);  // (released once it has completed)
+    HIP_TRY(e);
+    return PDWT_OK;
+}
+
 // four len x len banks of a non-separable plan, to banks `first` .. `first` + 3 (forward: 0, inverse: 4)
 int upload_f2d(pdwt_plan* p, int first, unsigned len, const real_t* const f[4]) {
     if (!p->d_f2d) HIP_TRY(device_malloc((void**)&p->d_f2d, (size_t)8 * kMaxTaps * kMaxTaps * sizeof(real_t)));
@@ -1881,10 +1893,15 @@ int pdwt_add_wavelet(pdwt_handle dst, pdwt_handle src, real_t alpha) {  // wt.cu
     DeviceGuard guard(dst->device);
     if (const int rc = settle(dst, Entry::add_wavelet)) return rc;
     if (const int rc = settle(src, Entry::add_wavelet)) return rc;
-    if (src->stream != dst->stream) HIP_TRY(hipStreamSynchronize(src->stream));
-    Stamp st(dst, "add_wavelet");
-    HIP_TRY(launch_axpy(dst->arena, src->arena, dst->coeff_elems, alpha, dst->stream));
-    return PDWT_OK;
+    // after what is queued on the source's stream, without stopping the host ...
+    if (const int rc = order_after(dst->stream, src->stream)) return rc;
+    {
+        Stamp st(dst, "add_wavelet");
+        HIP_TRY(launch_axpy(dst->arena, src->arena, dst->coeff_elems, alpha, dst->stream));
+    }
+    // ... and whatever the source's stream is given next waits until the sum has read the source: the caller's next call on
+    // `src` (a threshold, a forward, set_coeff) would otherwise overwrite coefficients the sum is still reading
+    return order_after(src->stream, dst->stream);
 }
 
 long long pdwt_get_image(pdwt_handle h, real_t* dst) {  // wt.cu:419-422

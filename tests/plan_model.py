@@ -27,12 +27,35 @@ What every method returns and the state it leaves are written down from the head
   circshift           0; the image is shifted when `inplace` (wt.cu:364-366), rows stay for 1D plans
   set_filters_*       0; forward also renames the wavelet (wt.cu:558-600)
 
+and, without a reference counterpart, from the header alone (pypwt_amd.h:133-194) and lazy_state.hpp:
+
+  band_stats, estimate_sigma, select
+                      0 in every state (Entry::read_stats: a pending threshold is applied first, a consumed one written back
+                      first -- the eager model has neither to do); the result goes to the plan's slot
+  threshold_bands, denoise, keep
+                      PDWT_ERR_STATE in state INVERSE with nothing done, slots included (Entry::band_sweep), else 0; the state does
+                      not change.  denoise leaves sigma, (BayesShrink) the sums and the table in the slots, keep threshold and
+                      kept; a HOST table of threshold_bands is staged in the table slot (plan.cpp: plan_sweep_bands), a device
+                      table is read where it is
+  read_band_stats, read_sigma, last_thresholds, last_sparsify
+                      pdwt_adaptive_slots / pdwt_sparsify_slots + pdwt_copy: every state, zeros until a call has written them (a
+                      clone's slots are its own: zeros)
+  take_band(num)      pdwt_wait_for_stream(plan, pdwt_get_stream(twin)), then pdwt_set_coeff(plan, pdwt_coeff_ptr(twin, num), num,
+                      1): set_coeff's row for the plan (band 0 re-arms the inverse), coeff_ptr's for the twin
+
+PDWT_ERR_UNSUPPORTED: plan.cpp refuses the per-band operators for more than 96 bands, more than 65535 images, a band of 2^31 values
+(ensure_adaptive) and the select for 2^32 swept values per image (select_magnitude_impl).  Non-separable, 1D and batched-1D plans
+are served (the rows of a 1D plan are pooled into one image: its bands are (1, rows, cols) here too).  Plans of PLANS that are
+refused: none -- the largest has 13 bands, 2000 images and 2^20 values per band.
+
 Arithmetic: transforms through oracle.forward / oracle.inverse (fp64 plans: double="full"; the non-separable plan level by level
-through oracle.nonsep_*_level), operators through tests/ops_ref.py.
+through oracle.nonsep_*_level), operators through tests/ops_ref.py, tests/adaptive_ref.py and tests/sparsify_ref.py.
 """
 import numpy as np
 
+import adaptive_ref
 import ops_ref
+import sparsify_ref
 from oracle import oracle
 
 INIT, FORWARD, INVERSE = 0, 1, 2
@@ -45,6 +68,15 @@ KINDS = ("forward", "inverse", "soft", "hard", "group", "shrink", "linf", "norm1
 # ... and the ones the reference's Python class has a method for (src/pypwt.pyx:64-615)
 REFERENCE_KINDS = ("forward", "inverse", "soft", "hard", "shrink", "norm1", "norm2sq", "add_dst", "add_src", "get_image",
                    "get_coeff", "get_region", "set_image", "set_coeff", "filt_fwd", "filt_inv")
+# the adaptive and K-term calls (pypwt_amd.h:133-194), the readers of their result slots, and the documented hand-over of device
+# data from one plan to another (take_band).  Seeds 1-5 are drawn from KINDS / REFERENCE_KINDS alone and stay what they were.
+READ_STATS = ("band_stats", "estimate_sigma", "select")     # lazy_state.hpp: Entry::read_stats
+BAND_SWEEP = ("threshold_bands", "denoise", "keep")         # ... Entry::band_sweep
+SLOT_READERS = ("read_band_stats", "read_sigma", "last_thresholds", "last_sparsify")
+NEW_KINDS = READ_STATS + BAND_SWEEP + SLOT_READERS + ("take_band",)
+ALL_KINDS = KINDS + NEW_KINDS
+# ... and the ones pypwt_amd.Wavelets has a method for (wavelets.py:158-295), beside the reference's
+CLASS_KINDS = REFERENCE_KINDS + READ_STATS + BAND_SWEEP + SLOT_READERS
 SITUATIONS = ("neither", "pending", "consumed")
 
 # beta classes on images of 0..255 (checked against the first forward's details by test_plan_model_cpu.py):
@@ -97,6 +129,29 @@ class Spec(object):
     def level_of(self, num):
         return self.levels if num == 0 else ((num - 1) // 3 + 1 if self.ndim == 2 else num)
 
+    def single(self):
+        """the same plan for one image (the Python class has no batch)"""
+        if self.batch == 1:
+            return self
+        return Spec(self.name, self.kind, self.wname, self.shape, self.levels, 1, self.prec, self.cycle, self.separable, self.custom, self.bound)
+
+    def swept_count(self, do_app):
+        """N of the K-term operators: the elements per image of the detail bands, and of band 0 with `do_app` (the rows of a 1D
+        plan are pooled: they are one image)"""
+        return sum(r * c for (r, c) in self.band_shapes()[0 if do_app else 1:])
+
+    def table(self, seed):
+        """[nbands][batch] thresholds of threshold_bands: 0.5 .. 30, NaN for the approximation and for one more (band, image), a
+        zero, and for one seed in four a negative entry"""
+        rng = np.random.default_rng([seed, 733])
+        T = rng.uniform(0.5, 30.0, (self.nbands, self.batch)).astype(self.dt)
+        T[0, :] = np.nan
+        T[1 + int(rng.integers(0, self.nbands - 1)), int(rng.integers(0, self.batch))] = np.nan
+        T[1, 0] = 0.0
+        if seed % 4 == 0:
+            T[self.nbands - 1, self.batch - 1] = -1.5
+        return T
+
 
 PLANS = [
     Spec("swt2-haar-64x96-L3", "swt2", "haar", (64, 96), 3),
@@ -121,8 +176,11 @@ PLANS = [
     Spec("swt2-haar-64x256-L3", "swt2", "haar", (64, 256), 3),
     Spec("swt2-db2-40x264-L3", "swt2", "db2", (40, 264), 3),
 ]
-SEEDS = (1, 2, 3, 4)   # the C-ABI sequences of every plan
-CLASS_SEED = 5         # the one through the Python class
+SEEDS = (1, 2, 3, 4)   # the C-ABI sequences of every plan, drawn from KINDS
+CLASS_SEED = 5         # the one through the Python class, drawn from REFERENCE_KINDS
+NEW_SEEDS = (6, 7)     # C ABI, drawn from ALL_KINDS
+CLASS_SEED_2 = 8       # the Python class, drawn from CLASS_KINDS
+GIVEN_SIGMA = 7.25
 LENGTH = 40
 
 
@@ -143,8 +201,17 @@ class PlanModel(object):
         banks = spec.banks()
         self.dec = self.rec = banks[0]
         self.norms_slot = None   # what norms_async / soft_threshold_norms left on the device: (sum |c|, sum c^2)
+        self._clear_slots()
         self.input = None        # the image the last forward() was given (before the cycle-spinning shift)
         self.source = None       # ... while the bands are its untouched transform with the plan's own bank, else None
+
+    def _clear_slots(self):
+        """the plan's own result slots (pdwt_adaptive_slots, pdwt_sparsify_slots): the workspace is zeroed when it is allocated"""
+        s = self.spec
+        self.stats_slot = np.zeros((s.nbands, s.batch, 2), dtype=np.float64)
+        self.sigma_slot = np.zeros(s.batch, dtype=np.float64)
+        self.table_slot = np.zeros((s.nbands, s.batch), dtype=s.dt)
+        self.sparsify_slot = (np.zeros(s.batch, dtype=s.dt), np.zeros(s.batch, dtype=np.uint64))
 
     # ---- layout
     def elems(self, num):
@@ -315,6 +382,57 @@ class PlanModel(object):
         self._store(ops_ref.axpy(self._flat(), src._flat(), alpha))
         return 0
 
+    # ---- the adaptive and K-term calls: the arithmetic is tests/adaptive_ref.py's and tests/sparsify_ref.py's.  The read-only
+    # ones are legal in every state; the sweeps return PDWT_ERR_STATE after inverse() with nothing done (pypwt_amd.h:162-165,
+    # 183-185).  Each leaves its result in the plan's slot, where the readers find it.
+    def band_stats(self):
+        self.stats_slot = adaptive_ref.band_stats(self.bands)
+        return 0
+
+    def estimate_sigma(self, skip_zeros=1):
+        self.sigma_slot = adaptive_ref.estimate_sigma(self.bands[adaptive_ref.noise_band(self.spec.ndim)], bool(skip_zeros))
+        return 0
+
+    def select(self, k, do_app=0):
+        self.sparsify_slot = sparsify_ref.select_magnitude(self.bands, k, do_app)
+        return 0
+
+    def keep(self, k, do_app=0):
+        if self.state == INVERSE:
+            return ERR_STATE
+        thr, kept, out = sparsify_ref.keep_largest(self.bands, k, do_app)
+        self.sparsify_slot = (thr, kept)
+        self._store(out)
+        return 0
+
+    def threshold_bands(self, table, op="soft", on_device=0):
+        if self.state == INVERSE:
+            return ERR_STATE
+        if not on_device:  # plan.cpp, plan_sweep_bands: a host table is staged into the plan's own table slot
+            self.table_slot = np.array(table, dtype=self.spec.dt)
+        self._store(adaptive_ref.threshold_bands(self.bands, table, op))
+        return 0
+
+    def denoise(self, method="BayesShrink", op="soft", sigma=None, skip_zeros=1):
+        if self.state == INVERSE:
+            return ERR_STATE
+        s = self.spec
+        if method == "BayesShrink":  # plan.cpp, pdwt_denoise_async: the sums are taken for this recipe only
+            self.stats_slot = adaptive_ref.band_stats(self.bands)
+        sg, T, out = adaptive_ref.denoise(self.bands, s.ndim, s.shape[0] * s.shape[1], method, op, sigma, bool(skip_zeros))
+        self.sigma_slot, self.table_slot = sg, T
+        self._store(out)
+        return 0
+
+    def adopt_table(self, before, table, op):
+        """denoise, second step: the sweep of `before` with the table the library made"""
+        self.table_slot = np.array(table, dtype=self.spec.dt)
+        self._store(adaptive_ref.threshold_bands(before, self.table_slot, op))
+
+    def take_band(self, src, num):
+        """pdwt_wait_for_stream(self, src's stream), then pdwt_set_coeff(self, pdwt_coeff_ptr(src, num), num, 1)"""
+        return self.set_coeff(src.bands[num], num)
+
     # ---- data movement
     def get_image(self):
         return self.image.size, self.image
@@ -356,6 +474,7 @@ class PlanModel(object):
         c.image = self.image.copy()
         c.bands = [b.copy() for b in self.bands]
         c.norms_slot = None
+        c._clear_slots()
         return c
 
     def circshift(self, sr, sc, inplace):
@@ -430,6 +549,30 @@ class PlanModel(object):
             return self.set_filters_forward(s.banks()[a[0]], bank_name(s, a[0])), None
         if k == "filt_inv":
             return self.set_filters_inverse(s.banks()[a[0]]), None
+        if k == "band_stats":
+            return self.band_stats(), self.stats_slot
+        if k == "estimate_sigma":
+            return self.estimate_sigma(a[0]), self.sigma_slot
+        if k == "select":
+            return self.select(a[0], a[1]), self.sparsify_slot
+        if k == "keep":
+            rc = self.keep(a[0], a[1])
+            return rc, (self.sparsify_slot if rc == 0 else None)
+        if k == "threshold_bands":
+            return self.threshold_bands(s.table(a[0]), a[1], a[2]), None
+        if k == "denoise":
+            rc = self.denoise(*a)
+            return rc, ((self.sigma_slot, self.table_slot) if rc == 0 else None)
+        if k == "read_band_stats":
+            return 0, self.stats_slot
+        if k == "read_sigma":
+            return 0, self.sigma_slot
+        if k == "last_thresholds":
+            return 0, (self.sigma_slot, self.table_slot)
+        if k == "last_sparsify":
+            return 0, self.sparsify_slot
+        if k == "take_band":
+            return self.take_band(twin, a[0]), None
         raise ValueError(op)
 
 
@@ -464,6 +607,11 @@ class Situation(object):
 
     def __init__(self):
         self.state, self.pending, self.consumed = FORWARD, False, False
+        # have the details possibly been zeroed since the last forward()?  Then the noise estimate may be 0 and a BayesShrink entry
+        # 0 / 0, which the table rule does not define: the generator gives such a denoise its noise level.  (No old kind asks.)
+        # ... `flat`: the image is the reconstruction of such coefficients, and its transform has them again
+        self.dead = self.flat = False
+        self.spec = None   # the generator's plan: without one every keep counts as zeroing
 
     def name(self):
         return "pending" if self.pending else ("consumed" if self.consumed else "neither")
@@ -471,6 +619,8 @@ class Situation(object):
     def would_refuse(self, kind, custom_name):
         inv = self.state == INVERSE
         if kind in ("soft", "hard", "group", "shrink", "linf", "soft_norms", "get_coeff", "get_coeff_at", "get_region", "inverse"):
+            return inv
+        if kind in BAND_SWEEP:
             return inv
         if kind in ("add_dst", "add_src"):
             return inv or custom_name
@@ -480,9 +630,18 @@ class Situation(object):
         k = op[0]
         if self.would_refuse(k, custom_name):
             return
+        if k in ("soft", "hard", "group", "soft_norms", "shrink") and len(op) > 1 and (op[1] >= BETAS["above"] or (k == "shrink" and op[1] == 0.0)):
+            self.dead = True
+        if k == "keep" and (self.spec is None or len(op) < 3 or min(np.atleast_1d(op[1])) < self.spec.swept_count(op[2]) - 1):
+            self.dead = True   # (K >= N - 1 zeroes one value at the most)
+        if k == "denoise" and (len(op) < 4 or op[3] is None):
+            # the estimate of a white-noise image makes m - var cancel: thresholds of var / sqrt(eps).  A given noise level (at most
+            # 9.0, against details of tens) leaves every band most of its values
+            self.dead = True
         if k == "forward":
-            self.state, self.pending, self.consumed = FORWARD, False, False
+            self.state, self.pending, self.consumed, self.dead = FORWARD, False, False, self.flat
         elif k == "inverse":
+            self.flat = self.dead
             self.state, self.consumed, self.pending = INVERSE, self.pending, False
         elif k in ("soft", "soft_norms"):
             beta, do_app = op[1], op[2]
@@ -494,22 +653,32 @@ class Situation(object):
         elif k in ("raw_read", "clone"):
             self.pending = self.consumed = False         # Pending::apply + Consumed::write_back
         elif k == "set_image":
+            self.flat = False
             self.consumed = False                        # Consumed::write_back; a pending threshold stays pending
             self.state = INIT
-        elif k == "set_coeff":
+        elif k in ("set_coeff", "take_band"):
+            if k == "set_coeff" and self.spec is not None and op[1] == adaptive_ref.noise_band(self.spec.ndim):
+                self.dead = False   # the noise band has values again: the estimate is not 0, and no table entry 0 / 0
             self.pending = self.consumed = False
             if op[1] == 0 and self.state == INVERSE:
                 self.state = FORWARD
+        elif k in READ_STATS:
+            self.pending = self.consumed = False         # Pending::apply + Consumed::write_back, as the norms
+        elif k in BAND_SWEEP:
+            self.pending = False                         # Pending::apply
 
 
-def generate(spec, seed, length=LENGTH, kinds=KINDS, count=None):
+def generate(spec, seed, length=LENGTH, kinds=KINDS, count=None, shared_workspace=False):
     """`length` calls on a plan that has just run its first forward().  Steered, not uniform: the next call is the kind that this
     sequence has used least in the current lazy situation, and the sequence keeps moving through the three situations; refusals
     are capped and at least three forward() and three inverse() run.  Deterministic in (plan, seed).  `count`: a table of
     (situation, kind) -> uses shared by several sequences (see sequences()), so that together they cover every pair."""
-    rng = np.random.default_rng([seed, PLANS.index(spec) if spec in PLANS else 99, 20241])
+    names = [p.name for p in PLANS]
+    plan_index = names.index(spec.name) if spec.name in names else 99
+    rng = np.random.default_rng([seed, plan_index, 20241])
     kinds = [k for k in kinds if not (k in ("filt_fwd", "filt_inv") and spec.hlen <= 2)]  # the 2-tap plans keep their bank
     sit = Situation()
+    sit.spec = spec
     if count is None:
         count = {}
     for s in SITUATIONS:
@@ -561,6 +730,25 @@ def generate(spec, seed, length=LENGTH, kinds=KINDS, count=None):
             return (kind, int(rng.integers(-70, 70)), int(rng.integers(-70, 70)), int(rng.integers(0, 2)))
         if kind in ("filt_fwd", "filt_inv"):
             return (kind, int(rng.integers(0, 3)))
+        if kind == "estimate_sigma":
+            return (kind, do_app)   # (skip_zeros)
+        if kind in ("select", "keep"):
+            # K out of {0, 1, N/4, N-1, N, N+5} of the swept count; on a batched plan one K per image half of the time
+            n = spec.swept_count(do_app)
+            ks = (0, 1, n // 4, n - 1, n, n + 5)
+            if spec.batch > 1 and norm:
+                return (kind, tuple(int(ks[i]) for i in rng.integers(0, len(ks), spec.batch)), do_app)
+            return (kind, int(ks[int(rng.integers(0, len(ks)))]), do_app)
+        if kind == "threshold_bands":
+            return (kind, fresh(), "hard" if norm else "soft", do_app)   # (seed of the table, op, the table is in device memory)
+        if kind == "denoise":
+            # the estimate (two in four; where the details may be zero the main loop sets the noise band first), one noise level, one
+            # per image
+            given = max(0, int(rng.integers(0, 4)) - 1)
+            sigma = None if given == 0 else (GIVEN_SIGMA if given == 1 else tuple(3.0 + i % 7 for i in range(spec.batch)))
+            return (kind, "VisuShrink" if norm else "BayesShrink", str(rng.choice(["soft", "hard"])), sigma, do_app)
+        if kind == "take_band":
+            return (kind, 0 if (sit.state == INVERSE and rng.random() < 0.5) else int(rng.integers(0, spec.nbands)))
         return (kind,)
 
     def emit(op):
@@ -579,6 +767,18 @@ def generate(spec, seed, length=LENGTH, kinds=KINDS, count=None):
     while len(ops) < length:
         left = length - len(ops)
         owed = max(0, 3 - ran["forward"]) + max(0, 3 - ran["inverse"])
+        if shared_workspace and len(ops) >= 8 and sit.state != INVERSE and left > owed + 10:
+            # once per sequence: the noise estimate and the K-term select share the radix-select workspace (both orders, nothing in
+            # between), then three host uploads through the one pinned buffer back to back: a table, noise levels, K
+            shared_workspace = False
+            n = spec.swept_count(0)
+            for op in (("estimate_sigma", 1), ("keep", n // 4, 0), ("estimate_sigma", 0), ("select", n - 1, 0),
+                       ("threshold_bands", fresh(), "soft", 0), ("denoise", "VisuShrink", "hard", tuple(3.0 + i % 7 for i in range(spec.batch)) if spec.batch > 1 else GIVEN_SIGMA, 1),
+                       ("keep", tuple(int(n // (2 + i % 3)) for i in range(spec.batch)) if spec.batch > 1 else n // 2, 1),
+                       # ... and the whole recipe behind them, on a noise band with values
+                       ("set_coeff", adaptive_ref.noise_band(spec.ndim), fresh(), 0), ("denoise", ("BayesShrink", "VisuShrink")[plan_index % 2], "soft", None, plan_index // 2 % 2)):
+                emit(op)
+            continue
         if owed and left <= owed + 2:  # the closing rounds
             emit(("forward",) if (sit.state == INVERSE or ran["inverse"] >= 3) else ("inverse",))
             continue
@@ -598,7 +798,12 @@ def generate(spec, seed, length=LENGTH, kinds=KINDS, count=None):
                 continue
         allowed = [k for k in kinds if refusals < max_refusals or not sit.would_refuse(k, custom_name)]
         least = min(count[(here, k)] for k in allowed)
-        emit(make(str(rng.choice([k for k in allowed if count[(here, k)] == least]))))
+        op = make(str(rng.choice([k for k in allowed if count[(here, k)] == least])))
+        if op[0] == "denoise" and op[3] is None and sit.dead and left < 2:
+            op = op[:3] + (GIVEN_SIGMA,) + op[4:]
+        if op[0] == "denoise" and op[3] is None and sit.dead:
+            emit(("set_coeff", adaptive_ref.noise_band(spec.ndim), fresh(), 0))   # the estimate needs a noise band that is not zero
+        emit(op)
     return ops
 
 
@@ -615,6 +820,16 @@ def sequences():
             for seed in SEEDS + (CLASS_SEED,):
                 kinds = REFERENCE_KINDS if seed == CLASS_SEED else KINDS
                 _SEQUENCES[(spec.name, seed)] = generate(spec, seed, kinds=kinds, count=tables.setdefault((spec.defers, seed == CLASS_SEED), {}))
+        # the seeds that also draw the adaptive and K-term calls: a pass and usage tables of their own, so that the ones above stay
+        # byte for byte what they were (tests/test_plan_model_cpu.py holds their digest)
+        tables = {}
+        for spec in PLANS:
+            for seed in NEW_SEEDS + (CLASS_SEED_2,):
+                kinds = CLASS_KINDS if seed == CLASS_SEED_2 else ALL_KINDS
+                # (the old kinds start three uses ahead in every situation: the new ones get there first)
+                table = tables.setdefault((spec.defers, seed == CLASS_SEED_2), {(s, k): 3 for s in SITUATIONS for k in KINDS})
+                _SEQUENCES[(spec.name, seed)] = generate(spec.single() if seed == CLASS_SEED_2 else spec, seed, kinds=kinds, count=table,
+                                                         shared_workspace=seed == NEW_SEEDS[-1])
     return _SEQUENCES
 
 

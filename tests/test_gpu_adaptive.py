@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import adaptive_ref
+from adaptive_check import _id, check_table, swept
 import ops_ref
 from golden_util import reconstruction_tol
 from oracle import oracle
@@ -22,10 +23,6 @@ PLANS = [("w",) + c for c in OPS_CASES] + [("b", 3, 61, 59, 0, "db2", 2), ("b", 
                                            ("w", (4096, 4096), 2, 0, "db4", 4)]
 SMALL = PLANS[:7]
 DTYPES = [np.float32, np.float64]
-
-
-def _id(p):
-    return "-".join(str(x).replace(" ", "") for x in p)
 
 
 class Plan(object):
@@ -79,11 +76,6 @@ def ref_of(plan):
         _REF[key] = dict(stats=adaptive_ref.band_stats(bands), sigma=adaptive_ref.estimate_sigma(nb, True),
                          sigma_all=adaptive_ref.estimate_sigma(nb, False))
     return _REF[key]
-
-
-def swept(band):
-    """the swept length of a band: all its images, padded to 64 values"""
-    return -(-band.size // 64) * 64
 
 
 class DevBuf(object):
@@ -233,38 +225,6 @@ def test_threshold_bands_row_table_negative_entries_and_padding(spec, dtype):
 
 
 # --------------------------------------------------------------------------------------------------------------- denoise
-def check_table(p, bands, sigma, got_T, method, ref_stats=None):
-    """The device's table against the reference's: the final rounding (2^-24, 2^-53 in fp64) plus A n 2^-52, A = m / |m - var| the
-    cancellation factor, m the reference's mean(c^2), n the element count.  A (band, image) whose |m - var - eps| is below the
-    band's sum bound may sit on either side of the max(., eps) and is left out; at most ONE per case."""
-    dt = np.dtype(p.dtype)
-    stats = adaptive_ref.band_stats(bands) if ref_stats is None else ref_stats
-    want_T = adaptive_ref.threshold_table(bands, sigma, method, p.nsamples, stats=stats)
-    assert np.all(np.isnan(got_T[0])) and got_T.dtype == dt and got_T.shape == (p.nbands, p.batch)
-    rounding = 2.0 ** -24 if dt == np.float32 else 2.0 ** -53
-    eps = float(np.finfo(dt).eps)
-    left_out, worst = 0, 0.0
-    for b in range(1, p.nbands):
-        n = bands[b][0].size
-        for i in range(p.batch):
-            g, r = float(got_T[b, i]), float(want_T[b, i])
-            if method == "VisuShrink":
-                assert abs(g - r) <= 2 * rounding * abs(r), (b, i, g, r)
-                continue
-            var = sigma[i] * sigma[i]
-            m = stats[b, i, 1] / n
-            if abs(m - var - eps) < 2.0 * swept(bands[b]) * 2.0 ** -53 * m:
-                left_out += 1
-                continue
-            A = m / abs(m - var)
-            bound = rounding + A * n * 2.0 ** -52
-            worst = max(worst, abs(g - r) / abs(r) / bound)
-            assert abs(g - r) <= bound * abs(r), (b, i, g, r, A, n)
-    assert left_out <= 1, left_out
-    print("denoise table %s %s %s: worst %.3g of the bound, %d left out" % (_id(p.spec), dt.name, method, worst, left_out))
-    return want_T
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
 @pytest.mark.parametrize("method,op", [("BayesShrink", "soft"), ("VisuShrink", "hard")])
 @pytest.mark.parametrize("spec", PLANS, ids=_id)

@@ -2,14 +2,21 @@
 tests/test_gpu_sequences.py runs on the GPU, checked by running generator + model here, without one.
 
 The conditions are on the INPUTS of the GPU test: if a seed violates one, the generator changes, not the cap."""
+import hashlib
 from collections import Counter
 
 import numpy as np
 import pytest
 
+import adaptive_ref
 import ops_ref
 import plan_model as pm
+import plan_stand_in
+import sparsify_ref
+from adaptive_check import left_out_pairs
 from oracle import oracle
+
+ALL_SEEDS = pm.SEEDS + (pm.CLASS_SEED,) + pm.NEW_SEEDS + (pm.CLASS_SEED_2,)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -128,8 +135,9 @@ def test_model_nonseparable_and_custom_banks():
 def runs():
     """every sequence of the GPU test through the model: {(plan, seed): [(op, situation before it, refused)]}"""
     out = {}
-    for spec in pm.PLANS:
-        for seed in pm.SEEDS + (pm.CLASS_SEED,):
+    for table_spec in pm.PLANS:
+        for seed in ALL_SEEDS:
+            spec = table_spec.single() if seed == pm.CLASS_SEED_2 else table_spec  # (generated for one image: the class has no batch)
             ops = pm.sequences()[(spec.name, seed)]
             assert ops == pm.sequences()[(spec.name, seed)] and len(ops) == pm.LENGTH
             rng = np.random.default_rng(seed)
@@ -141,9 +149,16 @@ def runs():
             twin = m.clone()
             sit, custom, rows = pm.Situation(), False, []
             for op in ops:
-                before = sit.name()
+                before, bands_before = sit.name(), m.bands
                 rc, _ = m.apply(op, twin=twin, shift=tuple(int(v) for v in rng.integers(0, 60, 2)))
                 no = pm.refused(op, rc)
+                if op[0] == "denoise" and not no:
+                    # the table rule of tests/adaptive_check.py leaves out at most one (band, image) pair per table, and is not
+                    # defined where a band AND the noise level are zero: no committed sequence may ask for more
+                    stats = m.stats_slot if op[1] == "BayesShrink" else None  # (the model took the sums of `bands_before` for it)
+                    assert left_out_pairs(spec.dt, bands_before, m.sigma_slot, op[1], stats) <= 1, (spec, seed, op)
+                    if op[1] == "BayesShrink":
+                        assert all(stats[b, i, 1] > 0 or m.sigma_slot[i] > 0 for b in range(1, spec.nbands) for i in range(spec.batch)), (spec, seed, op)
                 if not spec.cycle:  # (a cycle-spinning plan's add_wavelet also depends on the shifts the library draws)
                     assert no == sit.would_refuse(op[0], custom), (spec, seed, op)
                 sit.step(op, custom)
@@ -156,29 +171,47 @@ def runs():
 
 
 def test_sequences_are_deterministic_and_complete():
-    assert len(pm.sequences()) == len(pm.PLANS) * 5
+    assert len(pm.sequences()) == len(pm.PLANS) * len(ALL_SEEDS)
     spec = pm.PLANS[0]
     assert pm.generate(spec, 1) == pm.generate(spec, 1) and pm.generate(spec, 1) != pm.generate(spec, 2)
     for (name, seed), ops in pm.sequences().items():
-        kinds = pm.REFERENCE_KINDS if seed == pm.CLASS_SEED else pm.KINDS
+        kinds = {pm.CLASS_SEED: pm.REFERENCE_KINDS, pm.CLASS_SEED_2: pm.CLASS_KINDS}.get(seed, pm.KINDS if seed in pm.SEEDS else pm.ALL_KINDS)
         assert all(op[0] in kinds for op in ops)
     assert "run_ops(spec, ops)" in pm.as_python(spec, 1, pm.sequences()[(spec.name, 1)], 3)
 
 
+def test_the_old_seeds_sequences_are_byte_for_byte_what_they_were():
+    """seeds 1-4 and CLASS_SEED are drawn from the kinds they were always drawn from; the digest is of the generator's output before
+    the adaptive kinds existed"""
+    old = {key: ops for key, ops in pm.sequences().items() if key[1] in pm.SEEDS + (pm.CLASS_SEED,)}
+    assert len(old) == 5 * len(pm.PLANS)
+    assert hashlib.sha256(repr(sorted(old.items())).encode()).hexdigest() == "5451552a63852deb3cdc322a31de9345e64362f54629cef427b831f644392b08"
+
+
 def test_every_operation_kind_occurs_at_least_ten_times(runs):
-    n = Counter(op[0] for (name, seed), rows in runs.items() if seed != pm.CLASS_SEED for op, _, _ in rows)
+    n = Counter(op[0] for (name, seed), rows in runs.items() if seed in pm.SEEDS for op, _, _ in rows)
     assert all(n[k] >= 10 for k in pm.KINDS), sorted(n.items(), key=lambda t: t[1])[:5]
     n = Counter(op[0] for (name, seed), rows in runs.items() if seed == pm.CLASS_SEED for op, _, _ in rows)
     assert all(n[k] >= 10 for k in pm.REFERENCE_KINDS), sorted(n.items(), key=lambda t: t[1])[:5]
+    n = Counter(op[0] for (name, seed), rows in runs.items() if seed in pm.NEW_SEEDS for op, _, _ in rows)
+    assert all(n[k] >= 10 for k in pm.ALL_KINDS), sorted(n.items(), key=lambda t: t[1])[:5]
+    n = Counter(op[0] for (name, seed), rows in runs.items() if seed == pm.CLASS_SEED_2 for op, _, _ in rows)
+    assert all(n[k] >= 10 for k in pm.CLASS_KINDS), sorted(n.items(), key=lambda t: t[1])[:5]
 
 
 def test_every_call_follows_every_lazy_situation_at_least_twice(runs):
     """on the plans that defer (plan.cpp: can_defer_soft), through the C ABI"""
     n = Counter()
     for (name, seed), rows in runs.items():
-        if spec_of(name).defers and seed != pm.CLASS_SEED:
+        if spec_of(name).defers and seed in pm.SEEDS:
             n.update((before, op[0]) for op, before, _ in rows)
     missing = [(s, k, n[(s, k)]) for s in pm.SITUATIONS for k in pm.KINDS if n[(s, k)] < 2]
+    assert not missing, missing
+    n = Counter()
+    for (name, seed), rows in runs.items():
+        if spec_of(name).defers and seed in pm.NEW_SEEDS:
+            n.update((before, op[0]) for op, before, _ in rows)
+    missing = [(s, k, n[(s, k)]) for s in pm.SITUATIONS for k in pm.NEW_KINDS if n[(s, k)] < 2]
     assert not missing, missing
     assert sum(1 for p in pm.PLANS if p.defers) >= 10
 
@@ -229,6 +262,10 @@ ENTRY_OF_KIND = {
     "get_coeff": "get_coeff", "get_coeff_at": "get_coeff", "get_region": "get_coeff", "raw_read": "coeff_ptr",
     "set_coeff": "set_coeff", "set_image": "set_image", "clone": "clone",
     "get_image": "untouched", "get_image_at": "untouched", "circshift": "untouched", "filt_fwd": "untouched", "filt_inv": "untouched",
+    "band_stats": "read_stats", "estimate_sigma": "read_stats", "select": "read_stats",
+    "threshold_bands": "band_sweep", "denoise": "band_sweep", "keep": "band_sweep",
+    "read_band_stats": "untouched", "read_sigma": "untouched", "last_thresholds": "untouched", "last_sparsify": "untouched",
+    "take_band": "set_coeff",  # (of this plan; pdwt_coeff_ptr settles the producer, whose lazy state the sequences never touch)
 }
 
 
@@ -244,7 +281,7 @@ def test_the_librarys_lazy_state_table_is_the_models_and_the_documents():
         assert lib.emu_lazy_row(i, out) == 0, name
         rows[name] = tuple(out)
     assert lib.emu_lazy_row(len(ENTRIES), out) == -1, "an Entry this test does not know"
-    assert not [k for k in pm.KINDS if k not in ENTRY_OF_KIND], "a kind of the model without an Entry"
+    assert not [k for k in pm.ALL_KINDS if k not in ENTRY_OF_KIND], "a kind of the model without an Entry"
 
     def library(row, state, pending, consumed):
         """(pending, consumed) after settle() and, for Pending::consume, the success branch of pdwt_inverse"""
@@ -259,10 +296,10 @@ def test_the_librarys_lazy_state_table_is_the_models_and_the_documents():
             consumed = False
         return False, pending, consumed
 
-    for kind in pm.KINDS:
+    for kind in pm.ALL_KINDS:
         row = rows[ENTRY_OF_KIND[kind]]
         # soft / soft_norms with do_app: what the call owes the EARLIER threshold (without it the new one becomes pending, below)
-        op = {"soft": (kind, 12.0, 1, 0), "soft_norms": (kind, 12.0, 1, 0), "set_coeff": (kind, 1, 5)}.get(kind, (kind,))
+        op = {"soft": (kind, 12.0, 1, 0), "soft_norms": (kind, 12.0, 1, 0), "set_coeff": (kind, 1, 5), "take_band": (kind, 1)}.get(kind, (kind,))
         for state in (pm.FORWARD, pm.INVERSE):
             for pending, consumed in ((False, False), (True, False), (False, True)):
                 sit = pm.Situation()
@@ -284,7 +321,155 @@ def test_the_librarys_lazy_state_table_is_the_models_and_the_documents():
             sit.step((kind, 12.0, 0, 0), False)
             assert sit.pending and not sit.consumed and rows["soft"][1] == APPLY
 
-    # the entries without a kind: the literal rows of docs/KERNELS.md
-    assert rows["read_stats"] == rows["norms"] == (0, APPLY, WRITE_BACK)
-    assert rows["band_sweep"][:2] == (1, APPLY)
+    assert {ENTRY_OF_KIND[k] for k in pm.READ_STATS} == {"read_stats"} and {ENTRY_OF_KIND[k] for k in pm.BAND_SWEEP} == {"band_sweep"}
     assert rows["untouched"] == (0, KEEP, C_KEEP)
+
+
+# ------------------------------------------------------------------------------------------- the adaptive and K-term kinds
+def test_new_kinds_are_their_references_on_a_fixed_sequence():
+    """band_stats, estimate_sigma, select, keep, threshold_bands, denoise, the slot readers and take_band against
+    tests/adaptive_ref.py and tests/sparsify_ref.py called directly, with the return values and refusals of the header."""
+    s = spec_of("swt2-db4-128x136-L3-b3")
+    m = pm.PlanModel(s, s.image(7))
+    for kind in pm.SLOT_READERS:  # nothing has written them
+        rc, got = m.apply((kind,))
+        assert rc == 0 and all(not np.any(g) for g in (got if isinstance(got, tuple) else (got,))), kind
+    m.forward()
+    twin = m.clone()
+    bands = [b.copy() for b in m.bands]
+    rc, got = m.apply(("band_stats",))
+    assert rc == 0 and np.array_equal(got, adaptive_ref.band_stats(bands)) and got.shape == (10, 3, 2)
+    for skip in (1, 0):
+        rc, got = m.apply(("estimate_sigma", skip))
+        assert rc == 0 and np.array_equal(got, adaptive_ref.estimate_sigma(bands[3], bool(skip)))
+    n = s.swept_count(0)
+    assert n == 9 * 128 * 136 and s.swept_count(1) == 10 * 128 * 136
+    rc, got = m.apply(("select", (0, n // 4, n + 5), 0))
+    want = sparsify_ref.select_magnitude(bands, (0, n // 4, n + 5), 0)
+    assert rc == 0 and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and got[0][0] == np.inf and got[1][2] == n
+    assert all(ops_ref.same_bits(a, b) for a, b in zip(m.bands, bands)), "the read-only calls leave the coefficients alone"
+    rc, got = m.apply(("keep", n // 4, 1))
+    thr, kept, bands = sparsify_ref.keep_largest(bands, n // 4, 1)
+    assert rc == 0 and np.array_equal(got[0], thr) and np.array_equal(got[1], kept)
+    assert all(ops_ref.same_bits(a, b) for a, b in zip(m.bands, bands)) and np.array_equal(m.apply(("last_sparsify",))[1][1], kept)
+    T = s.table(908)
+    assert T.shape == (10, 3) and np.isnan(T[0]).all() and np.isnan(T[1:]).sum() == 1 and T[1, 0] == 0 and (T[9, 2] < 0) == (908 % 4 == 0)
+    assert m.apply(("threshold_bands", 908, "hard", 0))[0] == 0
+    bands = adaptive_ref.threshold_bands(bands, T, "hard")
+    assert all(ops_ref.same_bits(a, b) for a, b in zip(m.bands, bands))
+    assert ops_ref.same_bits(m.apply(("last_thresholds",))[1][1], T), "a host table is staged in the plan's own slot"
+    assert m.apply(("threshold_bands", 909, "soft", 1))[0] == 0 and ops_ref.same_bits(m.table_slot, T), "... a device table is not"
+    bands = adaptive_ref.threshold_bands(bands, s.table(909), "soft")
+    for method, mode, sigma, skip in (("BayesShrink", "soft", None, 1), ("VisuShrink", "hard", 7.25, 0), ("BayesShrink", "hard", (3.0, 4.0, 5.0), 1)):
+        before_stats = m.stats_slot
+        rc, got = m.apply(("denoise", method, mode, sigma, skip))
+        sg, T, out = adaptive_ref.denoise(bands, 2, 128 * 136, method, mode, sigma, bool(skip))
+        assert rc == 0 and np.array_equal(got[0], sg) and ops_ref.same_bits(got[1], T)
+        assert all(ops_ref.same_bits(a, b) for a, b in zip(m.bands, out))
+        if method == "BayesShrink":
+            assert np.array_equal(m.stats_slot, adaptive_ref.band_stats(bands))
+        else:
+            assert m.stats_slot is before_stats, "VisuShrink takes no sums"
+        if sigma is not None:
+            assert np.array_equal(sg, np.broadcast_to(np.asarray(sigma, dtype=np.float64), (3,)))
+        bands = out
+    # take_band: the twin's band, bit for bit; band 0 after inverse() re-arms it
+    assert m.apply(("take_band", 4), twin=twin) == (0, None) and ops_ref.same_bits(m.bands[4], twin.bands[4])
+    assert m.inverse() == 0
+    for op in (("keep", 5, 0), ("threshold_bands", 910, "soft", 0), ("denoise", "VisuShrink", "soft", None, 1)):
+        table = m.table_slot
+        assert m.apply(op) == (pm.ERR_STATE, None) and m.table_slot is table and m.state == pm.INVERSE, op
+    for op in (("band_stats",), ("estimate_sigma", 1), ("select", 3, 1)):
+        assert m.apply(op)[0] == 0 and m.state == pm.INVERSE, op
+    assert m.apply(("take_band", 2), twin=twin)[0] == 0 and m.state == pm.INVERSE
+    assert m.apply(("take_band", 0), twin=twin)[0] == 0 and m.state == pm.FORWARD and ops_ref.same_bits(m.bands[0], twin.bands[0])
+    assert not m.clone().stats_slot.any() and not m.clone().sparsify_slot[1].any(), "a clone's workspace is its own: zeros"
+    # the rows of a 1D plan are pooled: one image
+    s = spec_of("dwt1-sym8-3x4096-L5")
+    m = pm.PlanModel(s, s.image(7))
+    m.forward()
+    assert m.apply(("estimate_sigma", 1))[1].shape == (1,) and m.apply(("band_stats",))[1].shape == (6, 1, 2)
+    assert s.swept_count(0) == sum(b.size for b in m.bands[1:])
+
+
+def test_conditions_on_the_adaptive_sequences(runs):
+    new = {key: rows for key, rows in runs.items() if key[1] in pm.NEW_SEEDS}
+    # every refusal of a new kind is reached (PDWT_ERR_STATE of the three sweeps; no plan of PLANS is refused as unsupported)
+    for kind in pm.BAND_SWEEP:
+        assert sum(1 for rows in new.values() for op, _, no in rows if op[0] == kind and no) >= 2, kind
+        assert sum(1 for rows in new.values() for op, _, no in rows if op[0] == kind and not no) >= 10, kind
+    assert not [op for rows in new.values() for op, _, no in rows if no and op[0] in pm.READ_STATS + pm.SLOT_READERS + ("take_band",)]
+    # K over {0, 1, N/4, N-1, N, N+5}; one K per image on a batched plan
+    seen, per_image = set(), 0
+    for (name, seed), rows in new.items():
+        s = spec_of(name)
+        for op, _, _ in rows:
+            if op[0] in ("select", "keep"):
+                n = s.swept_count(op[2])
+                ks = op[1] if isinstance(op[1], tuple) else (op[1],)
+                per_image += isinstance(op[1], tuple) and len(set(op[1])) > 1
+                seen |= {{0: "0", 1: "1", n // 4: "N/4", n - 1: "N-1", n: "N", n + 5: "N+5"}.get(k, "other") for k in ks}
+    assert seen >= {"0", "1", "N/4", "N-1", "N", "N+5"} and per_image >= 3, (seen, per_image)
+    # tables from host and device memory, a negative entry; sigma estimated, one value, one per image
+    tables = [(spec_of(name), op) for (name, seed), rows in new.items() for op, _, no in rows if op[0] == "threshold_bands" and not no]
+    assert {op[3] for _, op in tables} == {0, 1} and {op[2] for _, op in tables} == {"soft", "hard"}
+    assert any((s.table(op[1])[1:] < 0).any() for s, op in tables), "no table with a negative entry"
+    sigmas = [op[3] for rows in new.values() for op, _, no in rows if op[0] == "denoise" and not no]
+    assert any(isinstance(s, float) for s in sigmas) and any(isinstance(s, tuple) and len(s) > 1 for s in sigmas)
+    # the generator sets the noise band before a denoise that estimates its noise level on details that may be zero
+    # (Situation.dead): the estimate must not thin out -- at least two of each of (BayesShrink, VisuShrink) x skip_zeros, and two
+    # per combination and seed on average
+    estimated = Counter((op[1], op[4]) for rows in new.values() for op, _, no in rows if op[0] == "denoise" and not no and op[3] is None)
+    assert all(estimated[(m, skip)] >= 2 for m in ("BayesShrink", "VisuShrink") for skip in (0, 1)), estimated
+    assert sum(estimated.values()) >= 16, estimated
+    # the noise estimate and the K-term select share a workspace: both orders on one plan with no transform in between, and three
+    # host uploads (a table, noise levels, K) through the one pinned buffer back to back
+    both = uploads = 0
+    for rows in new.values():
+        kinds = [op[0] for op, _, no in rows if not no]
+        pairs = set(zip(kinds, kinds[1:]))
+        both += bool(pairs & {("estimate_sigma", "keep"), ("estimate_sigma", "select")}) and bool(pairs & {("keep", "estimate_sigma"), ("select", "estimate_sigma")})
+        for (a, _, _), (b, _, _), (c, _, _) in zip(rows, rows[1:], rows[2:]):
+            uploads += (a[0] == "threshold_bands" and a[3] == 0 and b[0] == "denoise" and b[3] is not None and c[0] in ("keep", "select"))
+    assert both >= len(pm.PLANS) and uploads >= len(pm.PLANS), (both, uploads)
+
+
+@pytest.fixture(scope="module")
+def judge():
+    """test_gpu_sequences.run_ops, the comparator of the GPU test, with the model behind AbiPlan's interface as its subject"""
+    import test_gpu_sequences as tgs
+
+    def run(spec, ops, seed, defect=None):
+        return tgs.run_ops(spec, ops, seed, subject=lambda sp, image: plan_stand_in.ModelSubject(sp, image, defect=defect))
+    run.canned = tgs.canned_adaptive
+    return run
+
+
+SMALL = ["swt2-haar-64x96-L3", "swt2-db3-30x44-L2", "swt2-sym4-64x64-L2-cycle", "dwt2-custom9-64x68-L1", "dwt2-nonsep-48x56-L2",
+         "swt2-haar-64x96-L3-f64", "swt1-db2-1x100-L2", "dwt1-sym8-3x4096-L5", "swt2-db4-128x136-L3-b3"]
+
+
+@pytest.mark.parametrize("name", SMALL)
+def test_the_comparator_accepts_the_model_itself(judge, name):
+    """... on the sequences with the new kinds and on the named adaptive orderings: every check of the GPU test can be met, the
+    table rule included (no entry of a committed sequence is 0 / 0)"""
+    spec = spec_of(name)
+    for seed in pm.NEW_SEEDS:
+        judge(spec, pm.sequences()[(name, seed)], seed)
+    judge(spec, judge.canned(spec), 9)
+
+
+@pytest.mark.parametrize("defect", plan_stand_in.DEFECTS)
+def test_planted_defects_are_caught(judge, defect):
+    """each stand-in library with one defect fails the GPU test's comparator on a generated sequence of a small plan that defers"""
+    caught, tried = [], 0
+    for spec in pm.PLANS:
+        if spec.defers and spec.batch <= 3 and spec.shape[0] * spec.shape[1] <= 1 << 15 and len(caught) < 2:
+            for seed in pm.NEW_SEEDS:
+                tried += 1
+                try:
+                    judge(spec, pm.sequences()[(spec.name, seed)], seed, defect)
+                except AssertionError as e:
+                    caught.append((spec.name, seed, str(e).splitlines()[0]))
+    assert caught, defect
+    print("PLANTED %s: caught on %d of %d sequences, first: %s" % (defect, len(caught), tried, caught[0][2][:160]))
